@@ -43,6 +43,26 @@ def test_launcher_three_ranks():
     assert d["n_gpus"] == 3 and d["gather_ok"] is True
 
 
+def test_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs writes the last step's outputs as float64 .npy files,
+    the same from run to run; --steps is the number of timed steps and the
+    line carries ms_per_step, without and with --full."""
+    import numpy as np
+    got = []
+    for name, more in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        p = _run(["--config", "rehearsal", "--gpus", "1", "--steps", "4", "--warmup", "1",
+                  "--dump-outputs", str(d)] + more, _env())
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
+        assert line["steps"] == 4 and line["ms_per_step"] > 0
+        assert sorted(os.listdir(d)) == ["records.npy"]
+        got.append(np.load(d / "records.npy"))
+    assert got[0].dtype == np.float64 and got[0].shape == (100, 3)
+    assert np.array_equal(got[0], got[1])
+    assert np.array_equal(got[0][:, 2], got[0][:, 1] + 10)
+
+
 def test_world_mismatch_fails():
     env = _env()
     env.update(WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")

@@ -8,7 +8,7 @@ mkdir -p "$OUT"
 cd "$R"
 for c in c2 c1 c3 c4 c5; do
   echo "== $c ($(date +%T))"
-  timeout -k 10 300 python bench.py --config $c > "$OUT/$c.json" 2> "$OUT/$c.err"
+  timeout -k 10 300 python bench.py --full --config $c > "$OUT/$c.json" 2> "$OUT/$c.err"
   rc=$?
   echo "== $c rc=$rc"
   tail -c 400 "$OUT/$c.json"
