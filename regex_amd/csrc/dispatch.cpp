@@ -528,7 +528,7 @@ hipError_t run_find_iter(rure *re, DevTables *t, const BatchDev &b, const IterOu
   // search of the iteration is one of those, on a wave per haystack (lane 0
   // searches, the wave runs the Pike VM where a DfaSuffix scan quits).
   if (lane_search_ok(*t) && re->nfa_ok)
-    return launch_find_iter(b, t->has_dfa ? &t->f : nullptr, t->r, &t->n, false, 0, o, st, t->cus, sp, &t->m);
+    return launch_find_iter_wave(b, t->has_dfa ? &t->f : nullptr, t->r, t->n, o, st, t->cus, sp, &t->m);
   // Chunked speculative iteration (iter_scan.hip); otherwise one wave per
   // haystack.  With look-around (or a DFA that can quit) it needs the
   // stripped states (not an anchored regex) and a whole haystack (no span:
@@ -595,12 +595,12 @@ hipError_t run_find_iter(rure *re, DevTables *t, const BatchDev &b, const IterOu
           hipError_t e = scratch_malloc((void **)&qf, 8, st);
           if (e == hipSuccess) e = hipMemsetAsync(qf, 0, 4, st);
           if (e == hipSuccess)
-            e = launch_find_iter(b, fa, t->r, &t->n, true, chunk, o, st, t->cus, nullptr, nullptr, nullptr, qf);
+            e = launch_find_iter_chunked(b, *fa, t->r, chunk, o, st, t->cus, IterQuit::device_word(qf));
           if (e == hipSuccess) {
             BatchDev bf = b;
             bf.gate = qf;
             bf.gate_set = 1;
-            e = launch_find_iter(bf, fi, t->r, &t->n, true, chunk, o, st, t->cus, nullptr);
+            e = launch_find_iter_chunked(bf, *fi, t->r, chunk, o, st, t->cus, IterQuit::none());
           }
           if (qf) {
             const hipError_t e2 = scratch_free(qf, st);
@@ -610,7 +610,7 @@ hipError_t run_find_iter(rure *re, DevTables *t, const BatchDev &b, const IterOu
           return e;
         }
         bool q = false;
-        const hipError_t e = launch_find_iter(b, fa, t->r, &t->n, true, chunk, o, st, t->cus, sp, nullptr, &q);
+        const hipError_t e = launch_find_iter_chunked(b, *fa, t->r, chunk, o, st, t->cus, IterQuit::read_back(&q));
         if (e != hipSuccess || !q) {
           if (e == hipSuccess) note_fwd_path(-14);
           return e;
@@ -624,12 +624,12 @@ hipError_t run_find_iter(rure *re, DevTables *t, const BatchDev &b, const IterOu
     // nothing read back).  Spans, and knob iter_wave=0, keep the read-back of
     // the quit and the one-wave-per-haystack fallback (-13).
     if (fi->can_quit && !sp && re->nfa_ok && knob(Knob::IterWave) != 0) {
-      const hipError_t e = launch_find_iter(b, fi, t->r, &t->n, true, chunk, o, st, t->cus, nullptr);
+      const hipError_t e = launch_find_iter_chunked(b, *fi, t->r, chunk, o, st, t->cus, IterQuit::wave_served(&t->n));
       if (e == hipSuccess) note_fwd_path(-27);
       return e;
     }
     bool quit = false;
-    const hipError_t e = launch_find_iter(b, fi, t->r, &t->n, true, chunk, o, st, t->cus, sp, nullptr, &quit);
+    const hipError_t e = launch_find_iter_chunked(b, *fi, t->r, chunk, o, st, t->cus, IterQuit::read_back(&quit), sp);
     // last_fwd_path: -12 = the chunked iteration of a look-around regex
     // answered, -13 = it quit (the wave path answers)
     // (-21: the chunked iteration of the full automaton answered; -15: so,
@@ -638,7 +638,7 @@ hipError_t run_find_iter(rure *re, DevTables *t, const BatchDev &b, const IterOu
     if (e != hipSuccess || !quit) return e;
   }
   if (!re->nfa_ok) return hipErrorInvalidValue;
-  const hipError_t e = launch_find_iter(b, t->has_dfa ? &t->f : nullptr, t->r, &t->n, false, 0, o, st, t->cus, sp);
+  const hipError_t e = launch_find_iter_wave(b, t->has_dfa ? &t->f : nullptr, t->r, t->n, o, st, t->cus, sp);
   if (e == hipSuccess && last_fwd_path() != -13) note_fwd_path(-22);  // one haystack per wavefront
   return e;
 }

@@ -45,6 +45,11 @@ struct LaneState {
 static constexpr uint64_t NONE = ~0ull;
 static constexpr uint64_t QUITMARK = ~0ull - 1;
 
+// The descriptor with no hot rows: every step reads the global tables (for
+// kernels that stage no LDS image, or whose LDS holds something else).
+inline FwdDfaDev global_tables(FwdDfaDev f) { f.hot = 0; return f; }
+inline RevDfaDev global_tables(RevDfaDev r) { r.hot = 0; return r; }
+
 // The bookkeeping of entering state s at haystack position `pos`.
 template <int MODE>
 __device__ __forceinline__ void enter_state(LaneState &L, const FwdDfaDev &f, uint32_t s, uint64_t pos) {

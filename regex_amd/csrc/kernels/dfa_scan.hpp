@@ -19,6 +19,15 @@ constexpr uint32_t kIdCol = 256;
 
 enum { MODE_FIND = 0, MODE_ISMATCH = 1, MODE_SHORTEST = 2 };
 
+// The LDS hand-over inside one wave: what its lanes stored before it is what
+// its lanes load after it (the lanes run in lockstep, so no s_barrier; the
+// fences keep the compiler and the LDS queue from reordering across it).
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 struct BatchDev {
   const uint8_t *hay;
   const uint64_t *offs;   // n+1 offsets or nullptr (fixed stride)
@@ -334,16 +343,44 @@ struct IterSpan {
 // else null.
 hipError_t launch_find_iter_runs(const BatchDev &b, const uint8_t *cls, const uint32_t *cp, const IterOut &o,
                                  hipStream_t st, int cus, bool can_quit, bool *quit);
-hipError_t launch_find_iter(const BatchDev &b, const FwdDfaDev *f, const RevDfaDev &r, const NfaDev *nf,
-                            bool chunked, uint64_t chunk, const IterOut &o, hipStream_t st, int cus,
-                            const IterSpan *span = nullptr, const MatchDev *mt = nullptr, bool *quit = nullptr,
-                            uint32_t *quit_dev = nullptr);
-// (quit: chunked with a DFA that can quit, f->can_quit; set when a search
-// quit, the outputs then being void: the caller runs the wave path.  Reads
-// the flag back, so the call synchronises the stream.  quit_dev instead (a
-// zeroed device word, chunked, no span): a quit ORs 1 into it and the passes
-// after the speculative one run gated on it staying 0 -- nothing is read
-// back, and the caller enqueues its fallback gated on the word being set.)
+// find_iter with one wavefront per haystack (iter_scan.hip): per search the
+// DFA on one lane (f; null: no DFA) and the Pike VM on the wave where it quits
+// or is absent; mt: the reference's Literal / DfaSuffix searches instead.
+hipError_t launch_find_iter_wave(const BatchDev &b, const FwdDfaDev *f, const RevDfaDev &r, const NfaDev &nf,
+                                 const IterOut &o, hipStream_t st, int cus, const IterSpan *span = nullptr,
+                                 const MatchDev *mt = nullptr);
+// What the chunked find_iter does when a search's DFA quits (f.can_quit).
+struct IterQuit {
+  enum Kind {
+    // Nothing: for a DFA that cannot quit (hipErrorInvalidValue if it can).
+    None,
+    // *flag is set when a search quit, the outputs then being void: the
+    // caller runs the wave path.  Reads the flag back, so the call
+    // synchronises the stream.  A DFA that cannot quit leaves *flag alone.
+    ReadBack,
+    // word (device, zeroed): a quit ORs 1 into it and the passes after the
+    // speculative one run gated on it staying 0 -- nothing is read back, and
+    // the caller enqueues its fallback gated on the word being set.  Needs a
+    // DFA that can quit, an ungated batch and no span.
+    DeviceWord,
+    // The units whose searches quit are served by the Pike VM (nfa) on a wave
+    // inside the iteration; nothing is read back.  No span.
+    WaveServed,
+  } kind = None;
+  union {  // the selected kind's
+    bool *flag = nullptr;
+    uint32_t *word;
+    const NfaDev *nfa;
+  };
+  static IterQuit none() { return IterQuit(); }
+  static IterQuit read_back(bool *flag) { IterQuit q; q.kind = ReadBack; q.flag = flag; return q; }
+  static IterQuit device_word(uint32_t *word) { IterQuit q; q.kind = DeviceWord; q.word = word; return q; }
+  static IterQuit wave_served(const NfaDev *nfa) { IterQuit q; q.kind = WaveServed; q.nfa = nfa; return q; }
+};
+// The chunked speculative find_iter (iter_scan.hip): units of `chunk` bytes.
+hipError_t launch_find_iter_chunked(const BatchDev &b, const FwdDfaDev &f, const RevDfaDev &r, uint64_t chunk,
+                                    const IterOut &o, hipStream_t st, int cus, const IterQuit &quit,
+                                    const IterSpan *span = nullptr);
 // The k-mer probe engine of launch_find_iter_multi: the regexes' strings all
 // have one length len <= 8 over an alphabet of at most 4 bytes whose codes
 // (b >> shift) & 3 are distinct.  bitmap: 2048 u32, bit c set iff the L-mer
@@ -369,7 +406,7 @@ hipError_t launch_find_iter_multi(const BatchDev &b, int nre, const FwdDfaDev *c
                                   const KmerDev *km = nullptr);
 
 // One search per haystack over few long fixed-stride haystacks, chunked
-// (iter_scan.hip); f must be the find_iter DFA (with strip).
+// (long_scan.hip); f must be the find_iter DFA (with strip).
 hipError_t launch_long_scan(int mode, const BatchDev &b, const FwdDfaDev &f, const RevDfaDev &r, uint64_t chunk,
                             void *out, hipStream_t st, int cus);
 
@@ -417,7 +454,7 @@ double ktimer_read(uint64_t *launches);
 hipError_t launch_compact_matches(const uint64_t *found, uint64_t n, uint64_t base, uint64_t *rec, uint64_t cap,
                                   uint64_t *count, hipStream_t st);
 // find_iter from the batched find result when a haystack holds at most that
-// match (gather_scan.hip): counts, records, total as launch_find_iter.
+// match (gather_scan.hip): counts, records, total as IterOut's.
 hipError_t launch_find_to_iter(const uint64_t *found, uint64_t n, uint64_t *counts, uint64_t *matches, uint64_t cap,
                                uint64_t *total, hipStream_t st);
 // dst[i * words + w] = src (u8 0/1 or u64 mask) of haystack i (gather_scan.hip).

@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "dfa_device.hpp"
+#include "iter_device.hpp"
 #include "match_device.hpp"
 #include "nfa_device.hpp"
 
@@ -92,13 +93,6 @@ struct Unit {
 
 static_assert(sizeof(Unit) == 64, "iter_copy_group_kernel reads a unit's last 16 bytes");
 
-struct Geo {  // unit -> (haystack, chunk) for fixed-stride batches
-  uint64_t nk;      // units per haystack
-  uint64_t chunk;   // bytes per unit
-  uint64_t end;     // cut of the last unit (~0: the haystack end; a span's hi)
-  uint32_t slots;   // speculative matches stored per unit
-};
-
 // U_COMPACT slots are interleaved over the 64 units of a lexer wave (their
 // slot areas together, g.slots rows of 64 x 16 bytes): row k holds lexer
 // records 4k..4k+3 of every unit, lane by lane, so the lexer's per-tile row
@@ -126,22 +120,6 @@ __device__ __forceinline__ ulonglong2 slot_rec(const uint64_t *slots, const Geo 
     return ((const ulonglong2 *)slots)[lex_row16(g, u, g.slots - 1 - (i - nlex))];
   }
   return ((const ulonglong2 *)(slots + u * g.slots * 2))[i];
-}
-
-__device__ __forceinline__ void unit_bounds(const BatchDev &b, const Geo &g, uint64_t u, uint64_t *h,
-                                            const uint8_t **base, uint64_t *len, uint64_t *c0, uint64_t *c1) {
-  *h = u / g.nk;
-  const uint64_t k = u % g.nk;
-  if (b.offs) {
-    const uint64_t o0 = b.offs[*h], o1 = b.offs[*h + 1];
-    *base = b.hay + o0;
-    *len = o1 - o0;
-  } else {
-    *base = b.hay + *h * b.stride;
-    *len = b.length;
-  }
-  *c0 = b.start + k * g.chunk;
-  *c1 = (k + 1 == g.nk) ? g.end : b.start + (k + 1) * g.chunk;
 }
 
 // The wave's Pike VM for searches whose DFA quits (the wave-served chunked
@@ -266,21 +244,6 @@ __device__ __forceinline__ bool exit_equiv(bool ca, const IterSt &a, bool cb, co
   if (strict) return a.p == b.p && a.lm == b.lm;
   if (ca || cb) return ca && cb;
   return a.p == b.p && a.lm == b.lm;
-}
-
-// Dynamic LDS of the DFA kernels here: forward hot table, then the reverse
-// one (offset rev_lds_offset).
-__host__ __device__ inline uint32_t rev_lds_offset(uint32_t fwd_bytes) { return (fwd_bytes + 15) & ~15u; }
-inline size_t iter_lds_bytes(const FwdDfaDev &f, const RevDfaDev &r) { return rev_lds_offset(f.lds_bytes) + r.lds_bytes; }
-
-__device__ __forceinline__ const uint8_t *stage_tables(const FwdDfaDev &f, const RevDfaDev &r, uint8_t *lds) {
-  for (uint32_t i = threadIdx.x * 16; i < f.lds_bytes; i += blockDim.x * 16)
-    *(uint4 *)(lds + i) = *(const uint4 *)(f.lds_image + i);
-  uint8_t *rl = lds + rev_lds_offset(f.lds_bytes);
-  for (uint32_t i = threadIdx.x * 16; i < r.lds_bytes; i += blockDim.x * 16)
-    *(uint4 *)(rl + i) = *(const uint4 *)(r.lds_image + i);
-  __syncthreads();
-  return r.lds_bytes ? rl : nullptr;
 }
 
 // Branch-free exact steps for small automata (FwdDfaDev::all /
@@ -847,9 +810,7 @@ __global__ __launch_bounds__(256) void iter_spec_sa_tile_kernel(BatchDev b, Geo 
     for (uint64_t at = 0; at < C; at += 128) {
       RURE_STAGE(0, n0) RURE_STAGE(1, n1) RURE_STAGE(2, n2) RURE_STAGE(3, n3)
       RURE_STAGE(4, n4) RURE_STAGE(5, n5) RURE_STAGE(6, n6) RURE_STAGE(7, n7)
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_sync();
       const uint64_t an = at + 128 < C ? at + 128 : at;
       RURE_LOAD_TILE(an)
       if (full) {
@@ -863,9 +824,7 @@ __global__ __launch_bounds__(256) void iter_spec_sa_tile_kernel(BatchDev b, Geo 
           cur = nx;
         }
       }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_sync();
     }
 #undef RURE_LOAD_TILE
 #undef RURE_STAGE
@@ -1283,9 +1242,7 @@ __device__ __forceinline__ void multi_tile_body(const BatchDev &b, const Geo &g,
     for (uint64_t at = 0; at < C; at += 128) {
       RURE_STAGE(0, n0) RURE_STAGE(1, n1) RURE_STAGE(2, n2) RURE_STAGE(3, n3)
       RURE_STAGE(4, n4) RURE_STAGE(5, n5) RURE_STAGE(6, n6) RURE_STAGE(7, n7)
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_sync();
       const uint64_t an = at + 128 < C ? at + 128 : at;
       RURE_LOAD_TILE(an)
       if constexpr (KMER) {
@@ -1345,9 +1302,7 @@ __device__ __forceinline__ void multi_tile_body(const BatchDev &b, const Geo &g,
           cur = nx;
         }
       }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_sync();
     }
 #undef RURE_LOAD_TILE
 #undef RURE_STAGE
@@ -1628,9 +1583,7 @@ __global__ __launch_bounds__(256, 4) void iter_spec_lex_tile_kernel(BatchDev b, 
     for (uint64_t at = 0; at < C; at += 128) {
       RURE_STAGE(0, n0) RURE_STAGE(1, n1) RURE_STAGE(2, n2) RURE_STAGE(3, n3)
       RURE_STAGE(4, n4) RURE_STAGE(5, n5) RURE_STAGE(6, n6) RURE_STAGE(7, n7)
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_sync();
       const uint64_t an = at + 128 < C ? at + 128 : at;
       RURE_LOAD_TILE(an)
       // the tile's 8 blocks through the chain first (flag words kept), then
@@ -1684,9 +1637,7 @@ __global__ __launch_bounds__(256, 4) void iter_spec_lex_tile_kernel(BatchDev b, 
       for (int m = 0; m < 8; m += 2)
         if (16u * m < act) lex_events(mw[m], mw[m + 1], (uint32_t)at + 16 * m, cz, fc, last, n, Q, dst, cap4);
       Q.flush(dst, cap4);  // every lane, every tile (slots are padded to whole groups)
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_sync();
     }
 #undef RURE_LD
 #undef RURE_LOAD_TILE
@@ -2613,153 +2564,8 @@ hipError_t scan_counts(const uint32_t *counts, uint64_t *off, uint64_t n, hipStr
   return e != hipSuccess ? e : e2;
 }
 
-// Dynamic LDS beyond 64 KiB must be opted into per kernel (a gfx950
-// workgroup may use all 160 KiB).
-template <typename K>
-hipError_t allow_lds(K kernel, size_t bytes) {
-  if (bytes <= 64 * 1024) return hipSuccess;
-  return hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
-int grid_cap(uint64_t items, int threads, int cus, int per_cu) {
-  uint64_t g = (items + threads - 1) / threads;
-  uint64_t cap = (uint64_t)cus * per_cu;
-  if (g > cap) g = cap;
-  return (int)(g < 1 ? 1 : g);
-}
-
-// ------------------------------------------ one search over long haystacks
-// find / is_match / shortest_match (exec.rs:473-514, 382-420) when a batch
-// holds few, long haystacks: every unit scans its chunk with the cut-bounded
-// search (threads started in [c0, c1) only).  The leftmost-first match lives
-// in the first unit whose threads reach a match state: its forward end equals
-// the unrestricted search's (the earlier-started threads never match and the
-// later-started ones are cut by the match or never outrank it), and the
-// reverse pass runs over text[start..end] as the reference's does.  The
-// earliest match end (shortest_match) is the minimum over units.
-template <int MODE, bool PFX>
-__global__ __launch_bounds__(256) void long_scan_kernel(BatchDev b, Geo g, uint64_t nunits, FwdDfaDev f, RevDfaDev r,
-                                                        uint64_t *ures, unsigned long long *best) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-  const uint8_t *rlds = stage_tables(f, r, lds);
-  for (uint64_t u = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; u < nunits; u += (uint64_t)gridDim.x * blockDim.x) {
-    uint64_t h, len, c0, c1;
-    const uint8_t *base;
-    unit_bounds(b, g, u, &h, &base, &len, &c0, &c1);
-    LaneState L;
-    lane_start(L, f, base, len, c0);
-    if (c1 > c0 && c1 - 1 <= len) {
-      fwd_range<MODE, PFX>(L, f, lds, base, c0, c1 - 1);
-      if (!L.done) {
-        L.s = f.strip[L.s];
-        if (L.s == f.dead) L.done = true;
-      }
-      fwd_range<MODE>(L, f, lds, base, c1 - 1, len);
-    } else {
-      fwd_range<MODE, PFX>(L, f, lds, base, c0, len);
-    }
-    if (!L.done && f.eof[L.s]) L.last = len;
-    if (L.last == NONE) continue;
-    if (MODE == MODE_ISMATCH) {
-      ((uint8_t *)best)[h] = 1;  // best = the u8 output itself (long_scan_m)
-    } else if (MODE == MODE_SHORTEST) {
-      atomicMin(&best[h], (unsigned long long)L.last);  // the u64 output itself
-    } else {
-      uint64_t ms, me = L.last;
-      if (me == b.start) ms = me;  // exec.rs:647
-      else {
-        const uint64_t rs = rev_scan(r, rlds, base, len, b.start, me);
-        ms = rs;
-        if (rs == NONE) me = NONE;  // reverse NoMatch -> the search has no match
-      }
-      ures[2 * u] = ms;
-      ures[2 * u + 1] = me;
-      atomicMin(&best[h], (unsigned long long)u);
-    }
-  }
-}
-
-template <int MODE>
-__global__ void long_finish_kernel(uint64_t count, const uint64_t *ures, const unsigned long long *best, void *out) {
-  for (uint64_t h = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; h < count; h += (uint64_t)gridDim.x * blockDim.x) {
-    const unsigned long long v = best[h];
-    if (MODE == MODE_ISMATCH) {
-      ((uint8_t *)out)[h] = v == 1 ? 1 : 0;
-    } else if (MODE == MODE_SHORTEST) {
-      ((uint64_t *)out)[h] = v;
-    } else {
-      ((uint64_t *)out)[2 * h] = v == ~0ull ? NONE : ures[2 * v];
-      ((uint64_t *)out)[2 * h + 1] = v == ~0ull ? NONE : ures[2 * v + 1];
-    }
-  }
-}
-
-template <int MODE>
-hipError_t long_scan_m(const BatchDev &b, const FwdDfaDev &f, const RevDfaDev &r, uint64_t chunk, void *out,
-                       hipStream_t st, int cus) {
-  Geo g;
-  g.chunk = chunk;
-  g.end = ~0ull;
-  g.slots = 0;
-  const uint64_t span = b.length > b.start ? b.length - b.start : 0;
-  g.nk = span <= chunk ? 1 : (span + chunk - 1) / chunk;
-  const uint64_t nunits = b.count * g.nk;
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  // is_match / shortest_match write the output directly (a byte store / an
-  // atomic min per haystack): no scratch and no finish pass — the scratch
-  // cache's event per call had cost the latency-bound C1 step ~5 us
-  const size_t sz_u = MODE == MODE_FIND ? nunits * 16 : 0, sz_b = MODE == MODE_FIND ? b.count * 8 : 0;
-  uint8_t *buf = nullptr;
-  hipError_t e = MODE == MODE_FIND ? scratch_malloc((void **)&buf, al(sz_u) + al(sz_b), st) : hipSuccess;
-  if (e != hipSuccess) return e;
-  uint64_t *ures = (uint64_t *)buf;
-  unsigned long long *best = MODE == MODE_FIND ? (unsigned long long *)(buf + al(sz_u)) : (unsigned long long *)out;
-  do {
-    if (MODE == MODE_FIND)
-      e = hipMemsetAsync(best, 0xFF, sz_b, st);
-    else
-      e = hipMemsetAsync(out, MODE == MODE_ISMATCH ? 0 : 0xFF, b.count * (MODE == MODE_ISMATCH ? 1 : 8), st);
-    if (e != hipSuccess) break;
-    const int per_cu = std::max<int>(1, std::min<int>(8, (int)((160u * 1024u) / std::max<size_t>(iter_lds_bytes(f, r), 1))));
-    const dim3 lg(grid_cap(nunits, 256, cus, per_cu));
-    // the start-state prefix skip (fwd_range<MODE, true>) for one prefix
-    // first byte: measured faster there (Sherlock\s+\w+ 1.76 -> 1.54 ms per
-    // GiB, >[^\n]*\n 1.10 -> 0.31) and slower with two ((?i)holmes\w*:
-    // 1.46 -> 1.73 ms; profiles/r03_prefix_ab.jsonl)
-    if (f.pfx_n == 1 || f.rare_on) {
-      if ((e = allow_lds(long_scan_kernel<MODE, true>, iter_lds_bytes(f, r))) != hipSuccess) break;
-      hipLaunchKernelGGL((long_scan_kernel<MODE, true>), lg, dim3(256), iter_lds_bytes(f, r), st, b, g, nunits, f, r,
-                         ures, best);
-    } else {
-      if ((e = allow_lds(long_scan_kernel<MODE, false>, iter_lds_bytes(f, r))) != hipSuccess) break;
-      hipLaunchKernelGGL((long_scan_kernel<MODE, false>), lg, dim3(256), iter_lds_bytes(f, r), st, b, g, nunits, f, r,
-                         ures, best);
-    }
-    if ((e = hipGetLastError()) != hipSuccess) break;
-    if (MODE == MODE_FIND) {
-      hipLaunchKernelGGL(long_finish_kernel<MODE>, dim3(grid_cap(b.count, 256, cus, 4)), dim3(256), 0, st, b.count,
-                         (const uint64_t *)ures, (const unsigned long long *)best, out);
-      e = hipGetLastError();
-    }
-  } while (false);
-  hipError_t e2 = buf ? scratch_free(buf, st) : hipSuccess;
-  return e != hipSuccess ? e : e2;
-}
-
 }  // namespace
 
-hipError_t launch_long_scan(int mode, const BatchDev &b, const FwdDfaDev &f, const RevDfaDev &r, uint64_t chunk,
-                            void *out, hipStream_t st, int cus) {
-  note_fwd_path(-4);
-  switch (mode) {
-    case MODE_FIND: return long_scan_m<MODE_FIND>(b, f, r, chunk, out, st, cus);
-    case MODE_ISMATCH: return long_scan_m<MODE_ISMATCH>(b, f, r, chunk, out, st, cus);
-    default: return long_scan_m<MODE_SHORTEST>(b, f, r, chunk, out, st, cus);
-  }
-}
-
-// Unit geometry of a chunked find_iter: units of `chunk` bytes per haystack
-// (offset batches: one unit per haystack); returns the number of units.
 // Lexer engine (terminal matches + first-byte rule); RURE_AMD_LEX=0 disables.
 // (haystacks below 4 GiB: the lexer's records are u32 offsets from the unit
 // start, U_COMPACT; units of at most 64 KiB: its record queue packs two u16
@@ -2770,6 +2576,8 @@ static bool lex_usable(const FwdDfaDev &f, const BatchDev &b, const Geo &g) {
          b.length < (1ull << 32) && g.chunk <= 65536;
 }
 
+// Unit geometry of a chunked find_iter: units of `chunk` bytes per haystack
+// (offset batches: one unit per haystack); returns the number of units.
 static uint64_t iter_geo(const BatchDev &b, uint64_t chunk, uint64_t hi, Geo *g) {
   const uint64_t lim = std::min<uint64_t>(b.length, hi);
   const uint64_t span = (!b.offs && lim > b.start) ? lim - b.start : 0;
@@ -2812,10 +2620,17 @@ static hipError_t iter_scratch(uint64_t nunits, uint32_t nslots, hipStream_t st,
   return hipMemsetAsync(sc->qlen, 0, 16, st);  // qlen, dirty
 }
 
-static int iter_bs() {
+// Launch geometry of the per-unit passes that stage the hot tables (`lds`
+// bytes per block).  Threads per block: the tables are staged once per block,
+// so larger blocks let more waves share one LDS copy (occupancy of these
+// latency-bound per-lane scans); RURE_AMD_ITER_BS overrides (tuning).  Blocks
+// per CU: what its 2048 threads and 160 KiB of LDS hold.
+struct UnitLaunch { int bs, grid; };
+static UnitLaunch unit_launch(uint64_t nunits, size_t lds, int cus) {
   int bs = 256;
   if (knob(Knob::IterBs) > 0) bs = std::max(64, std::min<int>(1024, (int)knob(Knob::IterBs)));
-  return bs;
+  const int per_cu = std::max<int>(1, std::min<int>(2048 / bs, (int)((160u * 1024u) / std::max<size_t>(lds, 1))));
+  return {bs, grid_cap(nunits, bs, cus, per_cu)};
 }
 
 static bool sa_usable(const FwdDfaDev &f) {
@@ -2840,8 +2655,84 @@ struct WaveGeo {
 static hipError_t iter_post_body(const BatchDev &b, const Geo &g, uint64_t nunits, const FwdDfaDev &f,
                                  const RevDfaDev &r, const IterScratch &sc, const IterOut &o, const IterSpan *spn,
                                  hipStream_t st, int cus, bool dense, const NfaDev *wnf, uint8_t *wscr,
-                                 const WaveGeo &wg);
+                                 const WaveGeo &wg) {
+  hipError_t e;
+  const size_t lb = iter_lds_bytes(f, r);
+  const auto [bs, grid] = unit_launch(nunits, lb, cus);
+  if ((e = allow_lds(iter_fix_kernel, lb)) != hipSuccess || (e = allow_lds(iter_emit_kernel, lb)) != hipSuccess)
+    return e;
+  // the single-wave and wave kernels: global tables
+  const FwdDfaDev fw0 = global_tables(f);
+  const RevDfaDev rw0 = global_tables(r);
+  if (wnf) {
+    // The quit units' speculation: a wave answers the search that quit and
+    // hands the unit back to the lanes (kWaveRounds times: most units quit
+    // once or twice, at a cluster of non-ASCII bytes), then the waves finish
+    // what is still pending.
+    if ((e = allow_lds(iter_spec_burst_kernel, lb)) != hipSuccess) return e;
+    for (int k = 0; k < kWaveRounds; ++k) {
+      hipLaunchKernelGGL(iter_wspec_kernel<true>, dim3(wg.grid), dim3(wg.threads), wg.lds, st, b, g, nunits, fw0, rw0, *wnf,
+                         sc.units, sc.slots, sc.counts, sc.dirty, wscr, wg.mode);
+      if ((e = hipGetLastError()) != hipSuccess) return e;
+      hipLaunchKernelGGL(iter_spec_burst_kernel, dim3(grid), dim3(bs), lb, st, b, g, nunits, f, r, sc.units, sc.slots,
+                         sc.counts, sc.dirty, (uint32_t *)nullptr, 3u);
+      if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(iter_wspec_kernel<false>, dim3(wg.grid), dim3(wg.threads), wg.lds, st, b, g, nunits, fw0, rw0, *wnf,
+                       sc.units, sc.slots, sc.counts, sc.dirty, wscr, wg.mode);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  if (spn && spn->entry) {
+    hipLaunchKernelGGL(iter_entry_kernel, dim3(1), dim3(64), 0, st, b, g, nunits, fw0, rw0, sc.units, sc.counts,
+                       (const uint64_t *)sc.slots, spn->entry, sc.queue, sc.qlen);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  if (g.nk > 1) {
+    hipLaunchKernelGGL(iter_fix_kernel, dim3(grid), dim3(bs), lb, st, b, g, nunits, f, r, sc.units, sc.counts,
+                       (const uint64_t *)sc.slots, sc.queue, sc.qlen, (const uint32_t *)sc.dirty);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (wnf) {
+      hipLaunchKernelGGL(iter_wfix_kernel, dim3(wg.grid), dim3(wg.threads), wg.lds, st, b, g, nunits, fw0, rw0, *wnf, sc.units,
+                         sc.counts, (const uint64_t *)sc.slots, sc.queue, sc.qlen, (const uint32_t *)sc.dirty, wscr, wg.mode);
+      if ((e = hipGetLastError()) != hipSuccess) return e;
+      hipLaunchKernelGGL(iter_wwalk_kernel, dim3(1), dim3(64), wg.lds1, st, b, g, nunits, fw0, rw0, *wnf, sc.units,
+                         sc.counts, (const uint64_t *)sc.slots, sc.queue, sc.qlen, wscr, wg.mode);
+    } else {
+      hipLaunchKernelGGL(iter_walk_kernel, dim3(1), dim3(64), 0, st, b, g, nunits, fw0, rw0, sc.units, sc.counts,
+                         (const uint64_t *)sc.slots, sc.queue, sc.qlen);
+    }
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  if ((e = scan_counts(sc.counts, sc.off, nunits, st)) != hipSuccess) return e;
+  // a lexer pass (match-dense): its copies in output order first, then the
+  // emit pass only re-runs units (needs a 16-byte aligned output)
+  dense = dense && (((uintptr_t)o.matches) & 15) == 0;
+  if (dense) {
+    hipLaunchKernelGGL(iter_copy_group_kernel, dim3(grid_cap((nunits + 63) / 64, 1, cus, 8)), dim3(256), 0, st, b, g,
+                       nunits, (const Unit *)sc.units, (const uint64_t *)sc.slots, (const uint64_t *)sc.off, o.matches,
+                       o.cap);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(iter_emit_kernel, dim3(grid), dim3(bs), lb, st, b, g, nunits, f, r, sc.units, sc.slots, sc.off,
+                     o.matches, o.cap, dense ? 0 : 1);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if (wnf) {
+    hipLaunchKernelGGL(iter_wemit_kernel, dim3(wg.grid), dim3(wg.threads), wg.lds, st, b, g, nunits, fw0, rw0, *wnf,
+                       (const Unit *)sc.units, (const uint64_t *)sc.off, o.matches, o.cap, wscr, wg.mode);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(iter_counts_kernel, dim3(grid_cap(b.count, 256, cus, 4)), dim3(256), 0, st, b.count, g.nk,
+                     sc.off, o.counts, o.total, b);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if (spn && spn->exit) {
+    hipLaunchKernelGGL(iter_exit_kernel, dim3(1), dim3(64), 0, st, (const Unit *)sc.units, nunits, spn->exit,
+                       spn->tail, f.nonempty);
+    e = hipGetLastError();
+  }
+  return e;
+}
 
+// ... with the wave geometry chosen and its scratch held (wnf set)
 static hipError_t iter_post(const BatchDev &b, const Geo &g, uint64_t nunits, const FwdDfaDev &f, const RevDfaDev &r,
                             const IterScratch &sc, const IterOut &o, const IterSpan *spn, hipStream_t st, int cus,
                             bool dense = false, const NfaDev *wnf = nullptr) {
@@ -2889,93 +2780,6 @@ static hipError_t iter_post(const BatchDev &b, const Geo &g, uint64_t nunits, co
   e = iter_post_body(b, g, nunits, f, r, sc, o, spn, st, cus, dense, wnf, wscr, wg);
   const hipError_t e2 = scratch_free(wscr, st);
   return e != hipSuccess ? e : e2;
-}
-
-static hipError_t iter_post_body(const BatchDev &b, const Geo &g, uint64_t nunits, const FwdDfaDev &f,
-                                 const RevDfaDev &r, const IterScratch &sc, const IterOut &o, const IterSpan *spn,
-                                 hipStream_t st, int cus, bool dense, const NfaDev *wnf, uint8_t *wscr,
-                                 const WaveGeo &wg) {
-  hipError_t e;
-  const int bs = iter_bs();
-  const size_t lb = iter_lds_bytes(f, r);
-  const int per_cu = std::max<int>(1, std::min<int>(2048 / bs, (int)((160u * 1024u) / std::max<size_t>(lb, 1))));
-  const int grid = grid_cap(nunits, bs, cus, per_cu);
-  if ((e = allow_lds(iter_fix_kernel, lb)) != hipSuccess || (e = allow_lds(iter_emit_kernel, lb)) != hipSuccess)
-    return e;
-  FwdDfaDev fw0 = f;  // the wave kernels: global tables
-  fw0.hot = 0;
-  RevDfaDev rw0 = r;
-  rw0.hot = 0;
-  if (wnf) {
-    // The quit units' speculation: a wave answers the search that quit and
-    // hands the unit back to the lanes (kWaveRounds times: most units quit
-    // once or twice, at a cluster of non-ASCII bytes), then the waves finish
-    // what is still pending.
-    if ((e = allow_lds(iter_spec_burst_kernel, lb)) != hipSuccess) return e;
-    for (int k = 0; k < kWaveRounds; ++k) {
-      hipLaunchKernelGGL(iter_wspec_kernel<true>, dim3(wg.grid), dim3(wg.threads), wg.lds, st, b, g, nunits, fw0, rw0, *wnf,
-                         sc.units, sc.slots, sc.counts, sc.dirty, wscr, wg.mode);
-      if ((e = hipGetLastError()) != hipSuccess) return e;
-      hipLaunchKernelGGL(iter_spec_burst_kernel, dim3(grid), dim3(bs), lb, st, b, g, nunits, f, r, sc.units, sc.slots,
-                         sc.counts, sc.dirty, (uint32_t *)nullptr, 3u);
-      if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(iter_wspec_kernel<false>, dim3(wg.grid), dim3(wg.threads), wg.lds, st, b, g, nunits, fw0, rw0, *wnf,
-                       sc.units, sc.slots, sc.counts, sc.dirty, wscr, wg.mode);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  if (spn && spn->entry) {
-    FwdDfaDev fw = f;
-    fw.hot = 0;
-    RevDfaDev rw = r;
-    rw.hot = 0;
-    hipLaunchKernelGGL(iter_entry_kernel, dim3(1), dim3(64), 0, st, b, g, nunits, fw, rw, sc.units, sc.counts,
-                       (const uint64_t *)sc.slots, spn->entry, sc.queue, sc.qlen);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  if (g.nk > 1) {
-    hipLaunchKernelGGL(iter_fix_kernel, dim3(grid), dim3(bs), lb, st, b, g, nunits, f, r, sc.units, sc.counts,
-                       (const uint64_t *)sc.slots, sc.queue, sc.qlen, (const uint32_t *)sc.dirty);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (wnf) {
-      hipLaunchKernelGGL(iter_wfix_kernel, dim3(wg.grid), dim3(wg.threads), wg.lds, st, b, g, nunits, fw0, rw0, *wnf, sc.units,
-                         sc.counts, (const uint64_t *)sc.slots, sc.queue, sc.qlen, (const uint32_t *)sc.dirty, wscr, wg.mode);
-      if ((e = hipGetLastError()) != hipSuccess) return e;
-      hipLaunchKernelGGL(iter_wwalk_kernel, dim3(1), dim3(64), wg.lds1, st, b, g, nunits, fw0, rw0, *wnf, sc.units,
-                         sc.counts, (const uint64_t *)sc.slots, sc.queue, sc.qlen, wscr, wg.mode);
-    } else {
-      hipLaunchKernelGGL(iter_walk_kernel, dim3(1), dim3(64), 0, st, b, g, nunits, fw0, rw0, sc.units, sc.counts,
-                         (const uint64_t *)sc.slots, sc.queue, sc.qlen);
-    }
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  if ((e = scan_counts(sc.counts, sc.off, nunits, st)) != hipSuccess) return e;
-  // a lexer pass (match-dense): its copies in output order first, then the
-  // emit pass only re-runs units (needs a 16-byte aligned output)
-  dense = dense && (((uintptr_t)o.matches) & 15) == 0;
-  if (dense) {
-    hipLaunchKernelGGL(iter_copy_group_kernel, dim3(grid_cap((nunits + 63) / 64, 1, cus, 8)), dim3(256), 0, st, b, g,
-                       nunits, (const Unit *)sc.units, (const uint64_t *)sc.slots, (const uint64_t *)sc.off, o.matches,
-                       o.cap);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(iter_emit_kernel, dim3(grid), dim3(bs), lb, st, b, g, nunits, f, r, sc.units, sc.slots, sc.off,
-                     o.matches, o.cap, dense ? 0 : 1);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  if (wnf) {
-    hipLaunchKernelGGL(iter_wemit_kernel, dim3(wg.grid), dim3(wg.threads), wg.lds, st, b, g, nunits, fw0, rw0, *wnf,
-                       (const Unit *)sc.units, (const uint64_t *)sc.off, o.matches, o.cap, wscr, wg.mode);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(iter_counts_kernel, dim3(grid_cap(b.count, 256, cus, 4)), dim3(256), 0, st, b.count, g.nk,
-                     sc.off, o.counts, o.total, b);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  if (spn && spn->exit) {
-    hipLaunchKernelGGL(iter_exit_kernel, dim3(1), dim3(64), 0, st, (const Unit *)sc.units, nunits, spn->exit,
-                       spn->tail, f.nonempty);
-    e = hipGetLastError();
-  }
-  return e;
 }
 
 template <int NW, int MQ>
@@ -3180,9 +2984,7 @@ hipError_t launch_find_iter_multi(const BatchDev &b, int nre, const FwdDfaDev *c
     if (e != hipSuccess) break;
     if ((e = hipGetLastError()) != hipSuccess) break;
     // the passes of iter_post, each once for all regexes (blockIdx.y)
-    const int bs = iter_bs();
-    const int per_cu = std::max<int>(1, std::min<int>(2048 / bs, (int)((160u * 1024u) / std::max<size_t>(lb, 1))));
-    const uint32_t grid = (uint32_t)grid_cap(nunits, bs, cus, per_cu);
+    const auto [bs, grid] = unit_launch(nunits, lb, cus);
     if ((e = allow_lds(multi_fix_kernel, lb)) != hipSuccess || (e = allow_lds(multi_emit_kernel, lb)) != hipSuccess)
       break;
     if (entries) hipLaunchKernelGGL(multi_entry_kernel, dim3(1, nre), dim3(64), 0, st, b, g, nunits, ddesc);
@@ -3201,182 +3003,169 @@ hipError_t launch_find_iter_multi(const BatchDev &b, int nre, const FwdDfaDev *c
   return e != hipSuccess ? e : e2;
 }
 
-hipError_t launch_find_iter(const BatchDev &b, const FwdDfaDev *f, const RevDfaDev &r, const NfaDev *nf,
-                            bool chunked, uint64_t chunk, const IterOut &o, hipStream_t st, int cus,
-                            const IterSpan *spn, const MatchDev *mtd, bool *quit, uint32_t *quit_dev) {
-  const uint64_t hi = spn ? spn->hi : ~0ull;
-  if (quit_dev && (!chunked || spn || b.gate || !f || !f->can_quit)) return hipErrorInvalidValue;
-  // chunked, a DFA that can quit, no quit flag asked for: the wave-served
-  // iteration (the quit units' searches on the Pike VM; no span)
-  const bool wq = chunked && f && f->can_quit && !quit && !quit_dev && nf;
-  if (wq && spn) return hipErrorInvalidValue;
+hipError_t launch_find_iter_chunked(const BatchDev &b, const FwdDfaDev &f, const RevDfaDev &r, uint64_t chunk,
+                                    const IterOut &o, hipStream_t st, int cus, const IterQuit &quit,
+                                    const IterSpan *spn) {
+  bool ok = false;
+  switch (quit.kind) {
+    case IterQuit::None: ok = !f.can_quit; break;  // else nothing would write the quit units' matches
+    case IterQuit::ReadBack: ok = quit.flag != nullptr; break;
+    case IterQuit::DeviceWord: ok = quit.word && !spn && !b.gate && f.can_quit; break;
+    case IterQuit::WaveServed: ok = quit.nfa && !spn; break;
+  }
+  if (!ok) return hipErrorInvalidValue;
+  // (a DFA that cannot quit: ReadBack leaves the flag alone, no wave runs)
+  bool *const quit_host = quit.kind == IterQuit::ReadBack && f.can_quit ? quit.flag : nullptr;
+  uint32_t *const quit_dev = quit.kind == IterQuit::DeviceWord ? quit.word : nullptr;
+  const NfaDev *const wnf = quit.kind == IterQuit::WaveServed && f.can_quit ? quit.nfa : nullptr;
   hipError_t e = hipSuccess;
-  if (b.count == 0) {
-    return hipMemsetAsync(o.total, 0, 8, st);
+  if (b.count == 0) return hipMemsetAsync(o.total, 0, 8, st);
+  Geo g;
+  const uint64_t nunits = iter_geo(b, chunk, spn ? spn->hi : ~0ull, &g);
+  // Dense matches: the caller's capacity tells how many to expect; slots
+  // that hold them spare the emit pass re-running every unit (\b\w+\b over
+  // English, ~750 matches per 4 KiB unit: 128 slots re-ran them all, 19 of
+  // 33 ms).  Not for the lexer (its compact rows), at most 4 GiB.
+  if (!lex_usable(f, b, g) && !b.offs && o.cap > (uint64_t)g.slots * nunits) {
+    const uint64_t per = (o.cap + nunits - 1) / nunits;
+    const uint64_t want = std::min<uint64_t>(per + per / 4 + 4, std::min<uint64_t>(g.chunk + 1, 8192));
+    if (want > g.slots && want * nunits * 16 <= (4ull << 30)) g.slots = (uint32_t)want;
   }
-  if (chunked) {
-    Geo g;
-    const uint64_t nunits = iter_geo(b, chunk, hi, &g);
-    // Dense matches: the caller's capacity tells how many to expect; slots
-    // that hold them spare the emit pass re-running every unit (\b\w+\b over
-    // English, ~750 matches per 4 KiB unit: 128 slots re-ran them all, 19 of
-    // 33 ms).  Not for the lexer (its compact rows), at most 4 GiB.
-    if (!lex_usable(*f, b, g) && !b.offs && o.cap > (uint64_t)g.slots * nunits) {
-      const uint64_t per = (o.cap + nunits - 1) / nunits;
-      const uint64_t want = std::min<uint64_t>(per + per / 4 + 4, std::min<uint64_t>(g.chunk + 1, 8192));
-      if (want > g.slots && want * nunits * 16 <= (4ull << 30)) g.slots = (uint32_t)want;
+  IterScratch sc;
+  if ((e = iter_scratch(nunits, g.slots, st, &sc)) != hipSuccess) return e;
+  const size_t lb = iter_lds_bytes(f, r);
+  const auto [bs, grid] = unit_launch(nunits, lb, cus);
+  Unit *units = sc.units;
+  uint64_t *slots = sc.slots;
+  uint32_t *counts = sc.counts, *dirty = sc.dirty;
+  do {
+    if ((e = allow_lds(iter_spec_burst_kernel, lb)) != hipSuccess || (e = allow_lds(iter_fix_kernel, lb)) != hipSuccess ||
+        (e = allow_lds(iter_emit_kernel, lb)) != hipSuccess)
+      break;
+    // Literal engine: where the DFA does not fit LDS exactly (> 255 states,
+    // e.g. alternations of many words) it wins clearly (tools/lit_vs_dfa.py:
+    // 16 words 2.29 -> 0.72 ms, 64 words 5.43 -> 2.29 ms per GiB); with a
+    // small DFA it depends on the text (English -25 %, DNA +25 %), so the
+    // DFA stays.  Knob lit=1 / 0 forces it on / off.
+    // (a DFA that can quit takes the burst kernel: it alone hands quits
+    // and starts after a byte >= 0x80 over, iter_next)
+    const bool use_lit = !f.can_quit && f.lit_n && (knob(Knob::Lit) >= 0 ? knob(Knob::Lit) == 1 : !f.all);
+    // Shift-And engine for equal-length string sets; RURE_AMD_SA=0 disables
+    const bool use_sa = !f.can_quit && sa_usable(f);
+    const bool sa_tile = sa_tile_ok(b, g);
+    // Lexer engine (terminal matches + first-byte rule); RURE_AMD_LEX=0 disables
+    const bool use_lex = !f.can_quit && lex_usable(f, b, g);
+    // the quit flag (ReadBack): zeroed here, set by the burst kernel's first
+    // quit (the others stop) and by iter_quit_kernel
+    uint32_t *qd = quit_dev;
+    if (quit_host) {
+      if ((e = scratch_malloc((void **)&qd, 8, st)) != hipSuccess) break;
+      if ((e = hipMemsetAsync(qd, 0, 4, st)) != hipSuccess) { (void)scratch_free(qd, st); break; }
     }
-    IterScratch sc;
-    if ((e = iter_scratch(nunits, g.slots, st, &sc)) != hipSuccess) return e;
-    // threads per block: the hot tables are staged once per block, so larger
-    // blocks let more waves share one LDS copy (occupancy of these latency-
-    // bound per-lane scans); RURE_AMD_ITER_BS overrides (tuning)
-    const int bs = iter_bs();
-    const int per_cu = std::max<int>(1, std::min<int>(2048 / bs, (int)((160u * 1024u) / std::max<size_t>(iter_lds_bytes(*f, r), 1))));
-    const int grid = grid_cap(nunits, bs, cus, per_cu);
-    Unit *units = sc.units;
-    uint64_t *slots = sc.slots;
-    uint32_t *counts = sc.counts, *dirty = sc.dirty;
-    do {
-      const size_t lb = iter_lds_bytes(*f, r);
-      if ((e = allow_lds(iter_spec_burst_kernel, lb)) != hipSuccess || (e = allow_lds(iter_fix_kernel, lb)) != hipSuccess ||
-          (e = allow_lds(iter_emit_kernel, lb)) != hipSuccess)
-        break;
-      // Literal engine: where the DFA does not fit LDS exactly (> 255 states,
-      // e.g. alternations of many words) it wins clearly (tools/lit_vs_dfa.py:
-      // 16 words 2.29 -> 0.72 ms, 64 words 5.43 -> 2.29 ms per GiB); with a
-      // small DFA it depends on the text (English -25 %, DNA +25 %), so the
-      // DFA stays.  Knob lit=1 / 0 forces it on / off.
-      // (a DFA that can quit takes the burst kernel: it alone hands quits
-      // and starts after a byte >= 0x80 over, iter_next)
-      const bool use_lit = !f->can_quit && f->lit_n && (knob(Knob::Lit) >= 0 ? knob(Knob::Lit) == 1 : !f->all);
-      // Shift-And engine for equal-length string sets; RURE_AMD_SA=0 disables
-      const bool use_sa = !f->can_quit && sa_usable(*f);
-      const bool sa_tile = sa_tile_ok(b, g);
-      // Lexer engine (terminal matches + first-byte rule); RURE_AMD_LEX=0 disables
-      const bool use_lex = !f->can_quit && lex_usable(*f, b, g);
-      // the quit flag (a caller that re-runs on a quit): zeroed here, set by
-      // the burst kernel's first quit (the others stop) and by iter_quit_kernel
-      uint32_t *qd = quit_dev;
-      if (!qd && f->can_quit && quit) {
-        if ((e = scratch_malloc((void **)&qd, 8, st)) != hipSuccess) break;
-        if ((e = hipMemsetAsync(qd, 0, 4, st)) != hipSuccess) { (void)scratch_free(qd, st); break; }
-      }
-      ktimer_begin(st);  // bench diagnostics: the speculative kernel's duration
-      if (use_lex) {
-        const dim3 lg(grid_cap((nunits + 63) / 64, 4, cus, 4));
-        const bool one = b.count == 1;
-        if (f->lex4_image && one)
-          hipLaunchKernelGGL((iter_spec_lex_tile_kernel<true, true>), lg, dim3(256), 0, st, b, g, nunits, *f, units,
-                             slots, counts);
-        else if (f->lex4_image)
-          hipLaunchKernelGGL((iter_spec_lex_tile_kernel<true, false>), lg, dim3(256), 0, st, b, g, nunits, *f, units,
-                             slots, counts);
-        else if (one)
-          hipLaunchKernelGGL((iter_spec_lex_tile_kernel<false, true>), lg, dim3(256), 0, st, b, g, nunits, *f, units,
-                             slots, counts);
-        else
-          hipLaunchKernelGGL((iter_spec_lex_tile_kernel<false, false>), lg, dim3(256), 0, st, b, g, nunits, *f, units,
-                             slots, counts);
-        ktimer_end(st);
-        if ((e = hipGetLastError()) != hipSuccess) break;
-        if ((e = allow_lds(iter_lex_tail_kernel, lb)) != hipSuccess) break;
-        if (knob(Knob::LexTail) != 0)
-          hipLaunchKernelGGL(iter_lex_tail_kernel, dim3(grid_cap(nunits, 256, cus, 8)), dim3(256), lb, st, b, g, nunits,
-                           *f, r, units, slots, counts, dirty);
-      } else if (use_sa && sa_tile) {
-        const dim3 sg(grid_cap((nunits + 63) / 64, 4, cus, 4));
-        if (f->sa_bits <= 32)
-          hipLaunchKernelGGL((iter_spec_sa_tile_kernel<uint32_t>), sg, dim3(256), 0, st, b, g, nunits, *f, units,
-                             slots, counts, dirty);
-        else
-          hipLaunchKernelGGL((iter_spec_sa_tile_kernel<uint64_t>), sg, dim3(256), 0, st, b, g, nunits, *f, units,
-                             slots, counts, dirty);
-      } else if (use_sa) {
-        const dim3 sg(grid_cap(nunits, 256, cus, 8));
-        if (f->sa_bits <= 32)
-          hipLaunchKernelGGL((iter_spec_sa_kernel<uint32_t>), sg, dim3(256), 0, st, b, g, nunits, *f, units, slots,
-                             counts, dirty);
-        else
-          hipLaunchKernelGGL((iter_spec_sa_kernel<uint64_t>), sg, dim3(256), 0, st, b, g, nunits, *f, units, slots,
-                             counts, dirty);
-      } else if (use_lit) {
-        const dim3 lg(grid_cap(nunits, bs, cus, 2048 / bs));
-        if (f->lit_k8)
-          hipLaunchKernelGGL((iter_spec_lit_kernel<true, true>), lg, dim3(bs), kLitImage, st, b, g, nunits, *f, units,
-                             slots, counts, dirty);
-        else if (f->lit_k == 4)
-          hipLaunchKernelGGL((iter_spec_lit_kernel<true, false>), lg, dim3(bs), kLitImage, st, b, g, nunits, *f, units,
-                             slots, counts, dirty);
-        else
-          hipLaunchKernelGGL((iter_spec_lit_kernel<false, false>), lg, dim3(bs), kLitImage, st, b, g, nunits, *f,
-                             units, slots, counts, dirty);
-      } else {
-        hipLaunchKernelGGL(iter_spec_burst_kernel, dim3(grid), dim3(bs), iter_lds_bytes(*f, r), st, b, g, nunits, *f,
-                           r, units, slots, counts, dirty, qd, wq ? 1u : 0u);
-      }
-      if (!use_lex) ktimer_end(st);
-      if ((e = hipGetLastError()) != hipSuccess) {
-        if (qd && !quit_dev) (void)scratch_free(qd, st);
+    // one of the engines' speculative kernels (they share the leading arguments)
+    auto spec = [&](auto kernel, dim3 sgrid, dim3 block, size_t lds, auto... tail) {
+      hipLaunchKernelGGL(kernel, sgrid, block, lds, st, b, g, nunits, f, units, slots, counts, tail...);
+    };
+    ktimer_begin(st);  // bench diagnostics: the speculative kernel's duration
+    if (use_lex) {
+      const dim3 lg(grid_cap((nunits + 63) / 64, 4, cus, 4));
+      const bool one = b.count == 1;
+      if (f.lex4_image && one) spec(iter_spec_lex_tile_kernel<true, true>, lg, dim3(256), 0);
+      else if (f.lex4_image) spec(iter_spec_lex_tile_kernel<true, false>, lg, dim3(256), 0);
+      else if (one) spec(iter_spec_lex_tile_kernel<false, true>, lg, dim3(256), 0);
+      else spec(iter_spec_lex_tile_kernel<false, false>, lg, dim3(256), 0);
+      ktimer_end(st);
+      if ((e = hipGetLastError()) != hipSuccess) break;
+      if ((e = allow_lds(iter_lex_tail_kernel, lb)) != hipSuccess) break;
+      if (knob(Knob::LexTail) != 0)
+        hipLaunchKernelGGL(iter_lex_tail_kernel, dim3(grid_cap(nunits, 256, cus, 8)), dim3(256), lb, st, b, g, nunits,
+                           f, r, units, slots, counts, dirty);
+    } else if (use_sa && sa_tile) {
+      const dim3 sg(grid_cap((nunits + 63) / 64, 4, cus, 4));
+      if (f.sa_bits <= 32) spec(iter_spec_sa_tile_kernel<uint32_t>, sg, dim3(256), 0, dirty);
+      else spec(iter_spec_sa_tile_kernel<uint64_t>, sg, dim3(256), 0, dirty);
+    } else if (use_sa) {
+      const dim3 sg(grid_cap(nunits, 256, cus, 8));
+      if (f.sa_bits <= 32) spec(iter_spec_sa_kernel<uint32_t>, sg, dim3(256), 0, dirty);
+      else spec(iter_spec_sa_kernel<uint64_t>, sg, dim3(256), 0, dirty);
+    } else if (use_lit) {
+      const dim3 lg(grid_cap(nunits, bs, cus, 2048 / bs));
+      if (f.lit_k8) spec(iter_spec_lit_kernel<true, true>, lg, dim3(bs), kLitImage, dirty);
+      else if (f.lit_k == 4) spec(iter_spec_lit_kernel<true, false>, lg, dim3(bs), kLitImage, dirty);
+      else spec(iter_spec_lit_kernel<false, false>, lg, dim3(bs), kLitImage, dirty);
+    } else {
+      hipLaunchKernelGGL(iter_spec_burst_kernel, dim3(grid), dim3(bs), lb, st, b, g, nunits, f, r, units, slots,
+                         counts, dirty, qd, wnf ? 1u : 0u);
+    }
+    if (!use_lex) ktimer_end(st);
+    if ((e = hipGetLastError()) != hipSuccess) {
+      if (quit_host) (void)scratch_free(qd, st);
+      break;
+    }
+    // ORs 1 into *word if a unit's search quit
+    auto quit_check = [&](uint32_t *word) {
+      hipLaunchKernelGGL(iter_quit_kernel, dim3(grid_cap(nunits, 256, cus, 4)), dim3(256), 0, st, units, nunits, word);
+      return hipGetLastError();
+    };
+    // ... and reads the word back (synchronises the stream)
+    auto quit_read = [&](uint32_t *word, uint32_t *q) {
+      hipError_t qe = quit_check(word);
+      if (qe == hipSuccess) qe = hipMemcpyAsync(q, word, 4, hipMemcpyDeviceToHost, st);
+      return qe != hipSuccess ? qe : hipStreamSynchronize(st);
+    };
+    // DeviceWord: the quit check stays on the device and gates the rest
+    if (quit_dev) {
+      if ((e = quit_check(quit_dev)) != hipSuccess) break;
+      BatchDev bg = b;
+      bg.gate = quit_dev;
+      bg.gate_set = 0;
+      e = iter_post(bg, g, nunits, f, r, sc, o, spn, st, cus, use_lex);
+      break;
+    }
+    // ReadBack: a quit in the speculative pass ends the call here: the caller
+    // re-runs the batch on the full automaton or the wave path, and the fix
+    // walk over quit units is serial (the ASCII shadow over sherlock as it
+    // is, a non-ASCII byte every few KiB: 17 s; then 47.6 ms with the whole
+    // speculative pass run, against 38.4 ms on the full automaton alone;
+    // profiles/r05_shadow_bench.jsonl)
+    if (quit_host) {
+      uint32_t q = 0;
+      e = quit_read(qd, &q);
+      const hipError_t e2 = scratch_free(qd, st);
+      if (e == hipSuccess) e = e2;
+      if (e != hipSuccess) break;
+      if (q) {
+        *quit_host = true;
         break;
       }
-      // deferred: the quit check stays on the device and gates the rest
-      if (quit_dev) {
-        hipLaunchKernelGGL(iter_quit_kernel, dim3(grid_cap(nunits, 256, cus, 4)), dim3(256), 0, st, units, nunits,
-                           quit_dev);
-        if ((e = hipGetLastError()) != hipSuccess) break;
-        BatchDev bg = b;
-        bg.gate = quit_dev;
-        bg.gate_set = 0;
-        e = iter_post(bg, g, nunits, *f, r, sc, o, spn, st, cus, use_lex);
-        break;
-      }
-      // a quit in the speculative pass ends the call here: the caller re-runs
-      // the batch on the full automaton or the wave path, and the fix walk
-      // over quit units is serial (the ASCII shadow over sherlock as it is,
-      // a non-ASCII byte every few KiB: 17 s; then 47.6 ms with the whole
-      // speculative pass run, against 38.4 ms on the full automaton alone;
-      // profiles/r05_shadow_bench.jsonl)
-      if (qd) {
-        uint32_t q = 0;
-        if (e == hipSuccess) {
-          hipLaunchKernelGGL(iter_quit_kernel, dim3(grid_cap(nunits, 256, cus, 4)), dim3(256), 0, st, units, nunits,
-                             qd);
-          e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(&q, qd, 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        const hipError_t e2 = scratch_free(qd, st);
-        if (e == hipSuccess) e = e2;
-        if (e != hipSuccess) break;
-        if (q) {
-          *quit = true;
-          break;
-        }
-      }
-      e = iter_post(b, g, nunits, *f, r, sc, o, spn, st, cus, use_lex, wq ? nf : nullptr);
-      if (e == hipSuccess && f->can_quit && quit) {  // did any search quit?
-        uint32_t q = 0;
-        if ((e = hipMemsetAsync(dirty, 0, 4, st)) != hipSuccess) break;
-        hipLaunchKernelGGL(iter_quit_kernel, dim3(grid_cap(nunits, 256, cus, 4)), dim3(256), 0, st, units, nunits,
-                           dirty);
-        if ((e = hipMemcpyAsync(&q, dirty, 4, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
-        if ((e = hipStreamSynchronize(st)) != hipSuccess) break;
-        *quit = q != 0;
-      }
-    } while (false);
-    hipError_t e2 = scratch_free(sc.buf, st);
-    return e != hipSuccess ? e : e2;
-  }
-  // one wavefront per haystack (assertions, DFA quit, or no DFA)
-  const size_t wb = nfa_wave_bytes(nf->nleaves);
+    }
+    e = iter_post(b, g, nunits, f, r, sc, o, spn, st, cus, use_lex, wnf);
+    if (e == hipSuccess && quit_host) {  // did any search quit?
+      uint32_t q = 0;
+      if ((e = hipMemsetAsync(dirty, 0, 4, st)) != hipSuccess) break;
+      if ((e = quit_read(dirty, &q)) != hipSuccess) break;
+      *quit_host = q != 0;
+    }
+  } while (false);
+  hipError_t e2 = scratch_free(sc.buf, st);
+  return e != hipSuccess ? e : e2;
+}
+
+// One wavefront per haystack (assertions, DFA quit, or no DFA).
+hipError_t launch_find_iter_wave(const BatchDev &b, const FwdDfaDev *f, const RevDfaDev &r, const NfaDev &nf,
+                                 const IterOut &o, hipStream_t st, int cus, const IterSpan *spn,
+                                 const MatchDev *mtd) {
+  if (b.count == 0) return hipMemsetAsync(o.total, 0, 8, st);
+  const uint64_t hi = spn ? spn->hi : ~0ull;
+  const size_t wb = nfa_wave_bytes(nf.nleaves);
   const bool use_lds = wb <= kNfaLdsMax;
   const int grid = grid_cap(b.count, 1, cus, use_lds ? std::max<int>(1, std::min<int>(32, (int)((160u * 1024u) / wb))) : 4);
   uint8_t *buf = nullptr;
   const size_t sz_counts = (b.count + 1) * 4, sz_off = (b.count + 1) * 8;
   const size_t sz_scr = use_lds ? 0 : wb * (size_t)grid;
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  if ((e = scratch_malloc((void **)&buf, al(sz_counts) + al(sz_off) + al(sz_scr), st)) != hipSuccess) return e;
+  hipError_t e = scratch_malloc((void **)&buf, al(sz_counts) + al(sz_off) + al(sz_scr), st);
+  if (e != hipSuccess) return e;
   uint32_t *counts = (uint32_t *)buf;
   uint64_t *off = (uint64_t *)(buf + al(sz_counts));
   uint8_t *scr = use_lds ? nullptr : buf + al(sz_counts) + al(sz_off);
@@ -3385,21 +3174,15 @@ hipError_t launch_find_iter(const BatchDev &b, const FwdDfaDev *f, const RevDfaD
   const FwdDfaDev &fa = f ? *f : fz;
   const MatchDev md = mtd ? *mtd : MatchDev{-1, {}, {}, nullptr, 0};
   do {
-    if (lds > 64 * 1024) {
-      if ((e = hipFuncSetAttribute((const void *)iter_wave_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds)) != hipSuccess)
-        break;
-      if ((e = hipFuncSetAttribute((const void *)iter_wave_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds)) != hipSuccess)
-        break;
-    }
+    if ((e = allow_lds(iter_wave_kernel<false>, lds)) != hipSuccess) break;
+    if ((e = allow_lds(iter_wave_kernel<true>, lds)) != hipSuccess) break;
     if ((e = hipMemsetAsync(counts + b.count, 0, 4, st)) != hipSuccess) break;
-    hipLaunchKernelGGL(iter_wave_kernel<false>, dim3(grid), dim3(64), lds, st, b, fa, r, *nf, f ? 1 : 0, counts,
+    hipLaunchKernelGGL(iter_wave_kernel<false>, dim3(grid), dim3(64), lds, st, b, fa, r, nf, f ? 1 : 0, counts,
                        (const uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t)0, scr,
                        spn ? spn->entry : (const uint64_t *)nullptr, hi, spn ? spn->exit : (uint64_t *)nullptr, md);
     if ((e = hipGetLastError()) != hipSuccess) break;
     if ((e = scan_counts(counts, off, b.count, st)) != hipSuccess) break;
-    hipLaunchKernelGGL(iter_wave_kernel<true>, dim3(grid), dim3(64), lds, st, b, fa, r, *nf, f ? 1 : 0, counts,
+    hipLaunchKernelGGL(iter_wave_kernel<true>, dim3(grid), dim3(64), lds, st, b, fa, r, nf, f ? 1 : 0, counts,
                        (const uint64_t *)off, o.matches, o.cap, scr,
                        spn ? spn->entry : (const uint64_t *)nullptr, hi, (uint64_t *)nullptr, md);
     if ((e = hipGetLastError()) != hipSuccess) break;
@@ -3412,3 +3195,4 @@ hipError_t launch_find_iter(const BatchDev &b, const FwdDfaDev *f, const RevDfaD
 }
 
 }  // namespace rure_amd
+

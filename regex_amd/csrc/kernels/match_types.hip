@@ -182,8 +182,7 @@ hipError_t launch_suffix_long(int mode, const BatchDev &b, const MatchDev &m, co
                               const RevDfaDev &r, uint64_t chunk, void *out, uint8_t *status, hipStream_t st,
                               int cus) {
   note_fwd_path(-9);
-  FwdDfaDev fg = f;  // global-table stepping
-  fg.hot = 0;
+  FwdDfaDev fg = global_tables(f);  // global-table stepping
   fg.all = 0;
   fg.stride = 1;
   const uint64_t span = b.length - b.start;
@@ -235,8 +234,7 @@ hipError_t launch_suffix_long(int mode, const BatchDev &b, const MatchDev &m, co
 hipError_t launch_lane_search(int mode, const BatchDev &b, const MatchDev &m, const FwdDfaDev &f,
                               const RevDfaDev &r, void *out, hipStream_t st, int cus) {
   note_fwd_path(-5);
-  FwdDfaDev fg = f;  // global-table stepping (no LDS image staged)
-  fg.hot = 0;
+  FwdDfaDev fg = global_tables(f);  // global-table stepping (no LDS image staged)
   fg.all = 0;
   fg.stride = 1;
   const uint64_t blocks = (b.count + 255) / 256;
@@ -461,8 +459,7 @@ hipError_t scan_u64(bool inclusive, const T *in, T *out, size_t n, Op op, T init
 
 hipError_t launch_suffix_iter(const BatchDev &b, const MatchDev &m, const FwdDfaDev &f, const RevDfaDev &r,
                               uint64_t chunk, const IterOut &o, hipStream_t st, int cus) {
-  FwdDfaDev fg = f;  // global-table stepping
-  fg.hot = 0;
+  FwdDfaDev fg = global_tables(f);  // global-table stepping
   fg.all = 0;
   fg.stride = 1;
   const uint64_t span = b.length - b.start;

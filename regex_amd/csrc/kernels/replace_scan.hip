@@ -431,9 +431,7 @@ __global__ __launch_bounds__(256, 5) void replace_copy4_kernel(CopyCtx c, uint8_
     const uint64_t gs = w0 * kWin;
 #pragma unroll
     for (uint32_t q = 0; q < kGroupWin; ++q) A[64 * q + lane] = 0;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
 #pragma unroll
     for (uint32_t s = lane; s < kGroupSlots; s += 64) {  // slot s = match lo - 1 + s
       const int64_t g = (int64_t)lo - 1 + (int64_t)s;
@@ -448,9 +446,7 @@ __global__ __launch_bounds__(256, 5) void replace_copy4_kernel(CopyCtx c, uint8_
         if (bk < kGroupWin * 64) atomicAdd(&A[bk], 1u);
       }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     {  // inclusive prefix over the group's blocks (lane: blocks 4 lane .. 4 lane + 3)
       const uint4 a4 = *(const uint4 *)(A + 4 * lane);
       const uint32_t t = a4.x + a4.y + a4.z + a4.w;
@@ -463,9 +459,7 @@ __global__ __launch_bounds__(256, 5) void replace_copy4_kernel(CopyCtx c, uint8_
       ex -= t;
       *(uint4 *)(A + 4 * lane) = make_uint4(ex + a4.x, ex + a4.x + a4.y, ex + a4.x + a4.y + a4.z, ex + t);
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     uint4 v[kGroupWin];
     uint32_t fastm = 0;
 #pragma unroll
@@ -491,9 +485,7 @@ __global__ __launch_bounds__(256, 5) void replace_copy4_kernel(CopyCtx c, uint8_
       if (edge) sEdge[wv][ne + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)(64 * q + lane);
       ne += (uint32_t)__popcll(m);
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
 #pragma unroll 1
     for (uint32_t r0 = 0; r0 < ne; r0 += 64) {
       if (r0 + lane >= ne) continue;
@@ -564,9 +556,7 @@ __global__ __launch_bounds__(256, 5) void replace_copy4_kernel(CopyCtx c, uint8_
         push_rest(rest, rest_cap, nrest, p0);
       }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     lo = lo_n;
     hi = hi_n;
   }
@@ -883,12 +873,6 @@ __device__ __forceinline__ uint4 cls_block_slow(uint32_t r, uint32_t T, const ui
   return make_uint4(b[0], b[1], b[2], b[3]);
 }
 
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // A unit whose output spans at most kClsMap bytes from the aligned block
 // before it and holds at most kClsRank C bytes gets a block map: the output
 // offset of every replacement (P, by rank) and per 16-byte output block the
@@ -992,7 +976,7 @@ __global__ __launch_bounds__(256, CLS_WAVES) void replace_cls_write_kernel(const
     cls_load_co(hay, n, u, lane, v, &ua);
 #pragma unroll
     for (int j = 0; j < 4; ++j) *(uint4 *)(W.txt + tx(16 * lane + 1024 * j)) = v[j];
-    wave_sync();
+    wave_lds_sync();
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[j] = *(const uint4 *)(W.txt + tx(64 * lane + 16 * j));
     const uint32_t avail = ua > 64 * lane ? min(ua - 64 * lane, 64u) : 0u;
@@ -1076,7 +1060,7 @@ __global__ __launch_bounds__(256, CLS_WAVES) void replace_cls_write_kernel(const
     if (map) {
 #pragma unroll
       for (uint32_t i = 0; i < kClsCW; ++i) W.cnt[kClsCW * lane + i] = 0;
-      wave_sync();
+      wave_lds_sync();
       uint64_t mm = m;
       uint32_t P = o15 + r0, rk = kex;  // output offset of the next C byte from the aligned base, less c; its rank
       while (mm) {
@@ -1087,7 +1071,7 @@ __global__ __launch_bounds__(256, CLS_WAVES) void replace_cls_write_kernel(const
         W.P[rk++] = (uint16_t)q;
         P += L - 1;
       }
-      wave_sync();
+      wave_lds_sync();
       // exclusive prefix over the blocks (lane: words kClsCW lane ..)
       uint32_t cw[kClsCW];
 #pragma unroll
@@ -1110,7 +1094,7 @@ __global__ __launch_bounds__(256, CLS_WAVES) void replace_cls_write_kernel(const
         ex += cw[i] >> 16;
       }
     }
-    wave_sync();
+    wave_lds_sync();
     const uint64_t base = ob - o15, A = (ob + 15) & ~(uint64_t)15, E = ob + T, B = E & ~(uint64_t)15;
     // whole aligned blocks: text-only blocks from the staged text, the
     // others to the wave's slow list
@@ -1161,7 +1145,7 @@ __global__ __launch_bounds__(256, CLS_WAVES) void replace_cls_write_kernel(const
       // the list is worked off when full (a unit dense in replacements of a
       // long string has up to 256 L blocks) and after the unit's last round
       if (ns + 64 > kClsSlow || q0 + 1024 >= B) {
-        wave_sync();
+        wave_lds_sync();
 #pragma unroll 1
         for (uint32_t i0 = 0; i0 < ns; i0 += 64) {
           if (i0 + lane < ns) {
@@ -1182,7 +1166,7 @@ __global__ __launch_bounds__(256, CLS_WAVES) void replace_cls_write_kernel(const
           }
         }
         ns = 0;
-        wave_sync();
+        wave_lds_sync();
       }
     }
     // the edges: [ob, min(A, E)) and [max(B, A), E), byte by byte
@@ -1190,7 +1174,7 @@ __global__ __launch_bounds__(256, CLS_WAVES) void replace_cls_write_kernel(const
     const uint64_t pos = lane < 16 ? ob + lane : t0 + (lane - 16);
     const bool mine = lane < 16 ? pos < h1 : (lane < 32 && pos < E);
     if (mine && pos < cap) out[pos] = cls_out_byte((uint32_t)(pos - ob), W.rel, W.msk, W.txt, rep, L);
-    wave_sync();
+    wave_lds_sync();
   }
 }
 
@@ -1251,9 +1235,7 @@ __global__ __launch_bounds__(256) void hmap_count_kernel(const uint8_t *in, uint
       const uint64_t o = 16 * (uint64_t)lane + 1024 * j;
       *(uint4 *)(T + o) = o < av ? *(const uint4 *)(in + s0 + o) : make_uint4(0, 0, 0, 0);
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     // lane l counts dwords l, l + 64, ... (conflict-free reads); the changed
     // bytes (rare, but in nearly every step of some lane) are marked and
     // counted after the loop, so the loop has no branch
@@ -1283,9 +1265,7 @@ __global__ __launch_bounds__(256) void hmap_count_kernel(const uint8_t *in, uint
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) extra += __shfl_xor(extra, o);
     if (lane == 0) ucount[u] = extra;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     // (16-bit lane counters: at most 64 per unit; emptied every 512 units)
     if (reg && ++rounds == 512) {
       rounds = 0;
@@ -1394,17 +1374,13 @@ __global__ __launch_bounds__(256) void hmap_write_kernel(const uint8_t *in, uint
     {
       uint32_t pos = o15 + r0, nrest = 0;
       auto flush = [&]() {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         for (uint32_t e = lane; e < nrest; e += 64) {
           const uint32_t r = W.rest[e], inf = info[r & 0xFF], l = inf & 0x7F, off = inf >> 8;
           uint8_t *d = W.out + (r >> 8);
           for (uint32_t j = 1; j < l; ++j) d[j] = pool[off + j];
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         nrest = 0;
       };
 #pragma unroll
@@ -1439,9 +1415,7 @@ __global__ __launch_bounds__(256) void hmap_write_kernel(const uint8_t *in, uint
     const uint64_t pos = lane < 16 ? ob + lane : t0 + (lane - 16);
     const bool mine = lane < 16 ? pos < h1 : (lane < 32 && pos < E);
     if (mine && pos < cap) out[pos] = W.out[pos - base];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
   }
 }
 

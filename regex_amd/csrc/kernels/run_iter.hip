@@ -211,9 +211,7 @@ __global__ __launch_bounds__(256) void run_iter_kernel(BatchDev b, const uint8_t
         wrec[r - w0] = make_uint4((uint32_t)sp, (uint32_t)(sp >> 32), (uint32_t)e, (uint32_t)(e >> 32));
         ++r;
       }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_sync();
       const uint32_t nrec = min(kRunWin, T - w0);
       for (uint32_t j = lane; j < nrec; j += 64) {
         const uint64_t g = at0 + w0 + j;
@@ -227,9 +225,7 @@ __global__ __launch_bounds__(256) void run_iter_kernel(BatchDev b, const uint8_t
           }
         }
       }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_sync();
     }
   }
 }
