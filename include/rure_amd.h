@@ -206,6 +206,35 @@ int rure_amd_find_iter_span_multi(rure *const *res, size_t n, const uint8_t *hay
 int rure_amd_replace_batch(rure *re, const rure_amd_batch *batch, const uint8_t *rep, size_t rep_len,
                            size_t limit, uint8_t *out, uint64_t *out_offsets, size_t out_capacity,
                            uint64_t *total, void *stream);
+/* Batched replacen with a `$`-expanding template (bytes::Regex::replacen's
+ * captures path, re_bytes.rs:513-535): as rure_amd_replace_batch (out,
+ * out_offsets, out_capacity, total, limit: the same contract; batch->start
+ * must be 0), but rep[0..rep_len) is expanded per match as expand.rs:50-110
+ * does: `$N`, `$name`, `${...}` name a group (the longest run of
+ * [0-9A-Za-z_] after the `$`: `$1a` is the group named "1a"), `$$` is a `$`,
+ * an unknown group or one that did not participate expands to nothing.
+ * diverged (device, n bytes) as for rure_amd_captures_iter_batch, over the
+ * first `limit` matches of each haystack only: the output range
+ * [out_offsets[i], out_offsets[i + 1]) of a haystack with diverged[i] != 0 is
+ * not the reference's and must be recomputed by the caller from its
+ * sequential captures (see there).  A template that names no group but 0
+ * over a regex without look-around, and any template over a regex without
+ * groups, skip the captures pass (diverged stays 0).  Synchronises the stream
+ * to size the match buffer and once more before it returns.
+ * rure_amd_last_fwd_path: -29. */
+int rure_amd_replace_expand_batch(rure *re, const rure_amd_batch *batch, const uint8_t *rep, size_t rep_len,
+                                  size_t limit, uint8_t *out, uint64_t *out_offsets, size_t out_capacity,
+                                  uint64_t *total, uint8_t *diverged, void *stream);
+/* The compiled template of rure_amd_replace_expand_batch (host only, no
+ * GPU): pieces[3 * i ..] = (0, offset into lits, length) for a literal piece,
+ * (1, group, 0) for a group piece; references that expand to nothing for
+ * every match (an unknown name, a number >= the group count) are dropped and
+ * adjacent literals merged.  Returns the number of pieces (negative on
+ * error) and copies at most `cap` of them and at most `lits_cap` bytes of the
+ * literal pool, which is never longer than rep_len (NULL arrays: count
+ * only). */
+long rure_amd_expand_template_export(rure *re, const uint8_t *rep, size_t rep_len, uint32_t *pieces, size_t cap,
+                                     uint8_t *lits, size_t lits_cap);
 /* A chain of replace_all calls over one haystack, step i on step i - 1's
  * output: the regex-dna shootout's IUB substitutions
  * (examples/shootout-regex-dna-bytes.rs:44-60, each a bytes::Regex::
@@ -253,6 +282,37 @@ int rure_amd_compact_matches(const rure_match *found, size_t n, uint64_t base, u
 int rure_amd_captures_batch(rure *re, const rure_amd_batch *batch, size_t *slots, void *stream);
 /* Number of capture groups including group 0 (= rure_captures_len). */
 size_t rure_amd_captures_len(rure *re);
+/* Batched captures_iter (bytes::Regex::captures_iter, re_trait.rs:243-273):
+ * the groups of every successive match of every haystack.  batch->start must
+ * be 0 (RURE_AMD_ERR_ARG).  counts[i] (device) and *total (device) as for
+ * rure_amd_find_iter_batch; slots (device) receives min(total, capacity) rows
+ * of 2 * rure_amd_captures_len(re) entries, row j = the groups of the j-th
+ * match in haystack order as (start, end) relative to the haystack, SIZE_MAX
+ * where a group did not participate.
+ * The rows are computed in parallel over the batched find_iter's match list:
+ * the captures Pike VM runs from each match's start over the reference's cut
+ * window (exec.rs:555-567).  The reference iterates on the Pike VM's group 0
+ * instead; with a look-ahead at the cut (`(a..$)|(a)`) that can differ from
+ * the find_iter match, and then the rest of that haystack's sequence differs
+ * too.  diverged[i] (device, n bytes) is non-zero for such a haystack: its
+ * counts[i] and rows are NOT the reference's.  The caller redoes it alone:
+ * loop rure_find_captures(re, hay, len, last_end, caps) with CaptureMatches'
+ * rule (re_trait.rs:243-273: after an empty match (s == e) last_end = e + 1
+ * and the match is skipped if e == the previous match's end, else last_end =
+ * e; not rure_iter_next_captures' rule, which restarts one past the previous
+ * search start, regex-capi/src/rure.rs:363-397).  A regex without look-around
+ * or without groups never diverges.  (Where the reference's DFA quits, a
+ * Unicode \b next to a non-ASCII byte, its captures come from the whole text
+ * and the check is made against those.  As in rure_find_captures, the quit
+ * is decided with the reference's start-state prefix skip, dfa.rs:700-711: a
+ * non-ASCII byte that its DFA jumps over on the way to a prefix literal does
+ * not make it quit.)
+ * Synchronisation as for
+ * rure_amd_find_iter_batch's internal use by rure_amd_replace_batch: once to
+ * size the match buffer (twice if the first guess was short).
+ * rure_amd_last_fwd_path: -28. */
+int rure_amd_captures_iter_batch(rure *re, const rure_amd_batch *batch, uint64_t *counts, size_t *slots,
+                                 size_t capacity, uint64_t *total, uint8_t *diverged, void *stream);
 
 /* Returns the device scratch this library keeps cached for reuse (blocks
  * of the stream-ordered allocator freed by earlier batched calls; at most
@@ -446,7 +506,9 @@ int rure_amd_set_uses_dfa(rure_set *re);
  * engine of a C+ regex (its class over all bytes / the ASCII shadow's),
  * -21 = the chunked find_iter of the full automaton (no look-around), -22 =
  * find_iter with one haystack per wavefront, -23 = replace_all of a
- * one-byte-class regex without a match list; -1 before the first launch. */
+ * one-byte-class regex without a match list, -28 = the batched captures_iter
+ * (a wave per match), -29 = the batched replacen with a `$` template; -1
+ * before the first launch. */
 int rure_amd_last_fwd_path(void);
 /* Debug-only overrides of the engine dispatch and launch geometry
  * (regex_amd/csrc/host/knobs.hpp lists them): replaces the whole override

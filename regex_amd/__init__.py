@@ -181,6 +181,15 @@ def _batch(haystack, offsets=None, stride=None, length=None, count=None, start=0
     return b
 
 
+def _hay_bytes(haystack, b, offsets, h):
+    """Haystack h of a batch, read back to the host."""
+    if offsets is not None:
+        o0, o1 = (int(x) for x in offsets[h:h + 2].cpu().tolist())
+    else:
+        o0, o1 = h * b.stride, h * b.stride + b.length
+    return bytes(haystack.flatten()[o0:o1].cpu().numpy().tobytes())
+
+
 def _stream_ptr(stream):
     import torch
     s = stream if stream is not None else torch.cuda.current_stream()
@@ -401,6 +410,22 @@ class Regex(object):
         i = N.rure_capture_name_index(self._re, name.encode("utf-8"))
         return None if i < 0 else i
 
+    def expand_template(self, rep):
+        """The replacement template as the device expansion runs it
+        (rure_amd_expand_template_export; host only): ([(kind, a, b), ...],
+        lits) with (0, offset into lits, length) for a literal piece and
+        (1, group, 0) for a group piece."""
+        rep = bytes(rep)
+        n = N.rure_amd_expand_template_export(self._re, rep, len(rep), None, 0, None, 0)
+        if n < 0:
+            raise RuntimeError("expand_template failed (%d)" % n)
+        pieces = (ctypes.c_uint32 * max(3 * n, 1))()
+        lits = ctypes.create_string_buffer(max(len(rep), 1))
+        N.rure_amd_expand_template_export(self._re, rep, len(rep), pieces, n, lits, len(rep))
+        ps = [(pieces[3 * i], pieces[3 * i + 1], pieces[3 * i + 2]) for i in range(n)]
+        used = max([a + b for k, a, b in ps if k == 0] or [0])
+        return ps, lits.raw[:used]
+
     # ------------------------------------ replace / split (re_bytes.rs:316-535)
     def replacen(self, text, limit, rep):
         """Replaces the first `limit` matches (0 = all).  `rep` is bytes with
@@ -465,11 +490,20 @@ class Regex(object):
 
     # -------------------------------------------- batches (device tensors)
     def replace_batch(self, haystack, rep, limit=0, offsets=None, stride=None, length=None, count=None,
-                      stream=None):
-        """replacen over every haystack with a literal replacement (`$` is
-        not expanded; NoExpand semantics).  Returns (out, out_offsets): the
-        concatenated outputs (uint8) and n+1 int64 offsets into them."""
+                      stream=None, expand=False, resolve=True):
+        """replacen over every haystack.  Returns (out, out_offsets): the
+        concatenated outputs (uint8) and n+1 int64 offsets into them.
+
+        By default the replacement is literal (`$` is not expanded; NoExpand
+        semantics).  expand=True expands a bytes template on the device
+        (`$N`, `$name`, `${...}`, `$$`; rure_amd_replace_expand_batch); a
+        NoExpand, or a template without `$`, still takes the literal path.
+        Haystacks the device flags as diverged (a look-ahead made
+        captures_iter's matches differ from find_iter's) are read back,
+        replaced by the sequential `replacen` and spliced in; resolve=False
+        returns (out, out_offsets, diverged) with the raw device result."""
         import torch
+        expanding = expand and not isinstance(rep, NoExpand) and b"$" in bytes(rep)
         if isinstance(rep, NoExpand):
             rep = rep.rep
         rep = bytes(rep)
@@ -477,17 +511,102 @@ class Regex(object):
         dev = haystack.device
         ooff = torch.empty((b.count + 1,), dtype=torch.int64, device=dev)
         total = torch.zeros((1,), dtype=torch.int64, device=dev)
+        div = torch.zeros((max(b.count, 1),), dtype=torch.uint8, device=dev)[:b.count]
         cap = haystack.numel() + 1024
         while True:
             out = torch.empty((max(cap, 16) + 16,), dtype=torch.uint8, device=dev)
-            _check(N.rure_amd_replace_batch(self._re, ctypes.byref(b), rep, len(rep), limit,
-                                            ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ooff.data_ptr()), cap,
-                                            ctypes.c_void_p(total.data_ptr()), _stream_ptr(stream)), "replace_batch")
+            if expanding:
+                _check(N.rure_amd_replace_expand_batch(
+                    self._re, ctypes.byref(b), rep, len(rep), limit, ctypes.c_void_p(out.data_ptr()),
+                    ctypes.c_void_p(ooff.data_ptr()), cap, ctypes.c_void_p(total.data_ptr()),
+                    ctypes.c_void_p(div.data_ptr()), _stream_ptr(stream)), "replace_batch")
+            else:
+                _check(N.rure_amd_replace_batch(self._re, ctypes.byref(b), rep, len(rep), limit,
+                                                ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ooff.data_ptr()),
+                                                cap, ctypes.c_void_p(total.data_ptr()), _stream_ptr(stream)),
+                       "replace_batch")
             (stream or torch.cuda.current_stream()).synchronize()
             t = int(total.item())
             if t <= cap:
-                return out[:t], ooff
+                break
             cap = t
+        out = out[:t]
+        if not expanding:
+            return (out, ooff) if resolve or not expand else (out, ooff, div)
+        if not resolve:
+            return out, ooff, div
+        bad = torch.nonzero(div).flatten().cpu().tolist()
+        if bad:
+            oc = ooff.cpu()
+            lens, parts, last = oc[1:] - oc[:-1], [], 0
+            for h in bad:
+                parts.append(out[last:int(oc[h])])
+                fixed = self.replacen(_hay_bytes(haystack, b, offsets, h), limit, rep)
+                if fixed:
+                    parts.append(torch.frombuffer(bytearray(fixed), dtype=torch.uint8).to(dev))
+                lens[h] = len(fixed)
+                last = int(oc[h + 1])
+            parts.append(out[last:])
+            out = torch.cat(parts)
+            ooff = torch.zeros((b.count + 1,), dtype=torch.int64)
+            ooff[1:] = torch.cumsum(lens, 0)
+            ooff = ooff.to(dev)
+        return out, ooff
+
+    def captures_iter_batch(self, haystack, offsets=None, stride=None, length=None, count=None, capacity=None,
+                            stream=None, resolve=True):
+        """bytes::Regex::captures_iter over every haystack
+        (rure_amd_captures_iter_batch).  Returns (counts, groups, diverged):
+        counts = (n,) int64 matches per haystack, groups = (total, ngroups, 2)
+        int64 (start, end) per match in haystack order, -1 where a group did
+        not participate (at most `capacity` rows when given), diverged = (n,)
+        uint8 flags of the haystacks whose device rows were not the
+        reference's (a look-ahead made captures_iter's matches differ from
+        find_iter's).  Those are read back, redone by the sequential
+        `captures_iter` and spliced in; resolve=False returns the raw device
+        result, which is wrong exactly for the flagged haystacks."""
+        import torch
+        b = _batch(haystack, offsets, stride, length, count, 0)
+        dev = haystack.device
+        ng = self.captures_len()
+        counts = torch.empty((b.count,), dtype=torch.int64, device=dev)
+        total = torch.zeros((1,), dtype=torch.int64, device=dev)
+        div = torch.zeros((max(b.count, 1),), dtype=torch.uint8, device=dev)[:b.count]
+        cap = capacity if capacity is not None else max(1024, b.count * 4)
+        while True:
+            out = torch.empty((max(cap, 1), ng, 2), dtype=torch.int64, device=dev)
+            _check(N.rure_amd_captures_iter_batch(self._re, ctypes.byref(b), ctypes.c_void_p(counts.data_ptr()),
+                                                  ctypes.c_void_p(out.data_ptr()), cap,
+                                                  ctypes.c_void_p(total.data_ptr()), ctypes.c_void_p(div.data_ptr()),
+                                                  _stream_ptr(stream)), "captures_iter_batch")
+            (stream or torch.cuda.current_stream()).synchronize()
+            t = int(total.item())
+            if t <= cap:
+                break
+            if capacity is not None and not (resolve and bool(div.any().item())):
+                break
+            cap = t  # no capacity given, or a splice that needs every row
+        out = out[:min(t, cap)]
+        if not resolve or b.count == 0:
+            return counts, out, div
+        bad = torch.nonzero(div).flatten().cpu().tolist()
+        if bad:
+            cc = counts.cpu()
+            mo = [0] + torch.cumsum(cc, 0).tolist()
+            parts, last = [], 0
+            for h in bad:
+                parts.append(out[last:mo[h]])
+                rows = [[g if g is not None else (-1, -1) for g in c]
+                        for c in self.captures_iter(_hay_bytes(haystack, b, offsets, h))]
+                parts.append(torch.tensor(rows, dtype=torch.int64).reshape(len(rows), ng, 2).to(dev))
+                cc[h] = len(rows)
+                last = mo[h + 1]
+            parts.append(out[last:])
+            out = torch.cat(parts)
+            counts = cc.to(dev)
+            if capacity is not None:
+                out = out[:capacity]
+        return counts, out, div
 
     def split_batch(self, haystack, limit=None, offsets=None, stride=None, length=None, count=None,
                     capacity=None, stream=None):

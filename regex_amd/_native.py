@@ -129,6 +129,12 @@ rure_amd_split_batch = _sig("rure_amd_split_batch", ctypes.c_int, VP, ctypes.POI
                             c_size, VP, VP)
 rure_amd_captures_batch = _sig("rure_amd_captures_batch", ctypes.c_int, VP, ctypes.POINTER(RureBatch), VP, VP)
 rure_amd_captures_len = _sig("rure_amd_captures_len", c_size, VP)
+rure_amd_captures_iter_batch = _sig("rure_amd_captures_iter_batch", ctypes.c_int, VP, ctypes.POINTER(RureBatch), VP,
+                                    VP, c_size, VP, VP, VP)
+rure_amd_replace_expand_batch = _sig("rure_amd_replace_expand_batch", ctypes.c_int, VP, ctypes.POINTER(RureBatch),
+                                     ctypes.c_char_p, c_size, c_size, VP, VP, c_size, VP, VP, VP)
+rure_amd_expand_template_export = _sig("rure_amd_expand_template_export", ctypes.c_long, VP, ctypes.c_char_p, c_size,
+                                       VP, c_size, VP, c_size)
 rure_amd_nfa_saves_export = _sig("rure_amd_nfa_saves_export", ctypes.c_int, VP, VP, VP, ctypes.POINTER(c_size))
 rure_amd_dfa_info_get = _sig("rure_amd_dfa_info_get", ctypes.c_int, VP, ctypes.c_int, ctypes.POINTER(DfaInfo))
 rure_amd_set_dfa_info_get = _sig("rure_amd_set_dfa_info_get", ctypes.c_int, VP, ctypes.POINTER(DfaInfo))

@@ -674,6 +674,32 @@ DevTables *regex_device(rure *re, std::string *err) {
   const bool mt_lane = needs_mt_lane(re->xl);
   LitOffsets lp{}, ls{};
   size_t o_lcs = 0;
+  // SkipDfaDev: the raw forward automaton and the prefix literals, for a
+  // regex whose captures depend on whether the reference's DFA quits (groups
+  // beyond 0, a Unicode word boundary) and whose DFA has the start-state
+  // prefix skip (has_prefix, dfa.rs:1562-1566, under MatchType::Dfa)
+  const bool skip = re->dfa_ok && re->nfa_ok && re->fwd.has_unicode_word_boundary && !re->nfa.anchored_start &&
+                    re->xl.match_type == MT_DFA && re->xl.prefixes.matcher != 0 &&
+                    !re->xl.prefixes.lits.lits.empty() && re->nfa.capture_names.size() > 1;
+  DenseDfa raw;
+  LitOffsets lk{};
+  size_t o_kfull = 0, o_keof = 0, o_kstart = 0;
+  bool skip_ok = false;
+  if (skip) {
+    DfaBuildLimits lim;
+    lim.minimise = false;
+    std::string e;
+    if (build_dense_dfa(re->fwd, lim, &raw, &e) && raw.nstates <= 65535) {
+      std::vector<uint16_t> kfull(raw.trans.size()), kstart(128);
+      for (size_t i = 0; i < raw.trans.size(); ++i) kfull[i] = (uint16_t)raw.trans[i];
+      for (int i = 0; i < 128; ++i) kstart[i] = (uint16_t)raw.start[i];
+      o_kfull = b.add(kfull.data(), kfull.size() * 2);
+      o_keof = b.add(raw.eof_match.data(), raw.eof_match.size());
+      o_kstart = b.add(kstart.data(), 256);
+      lk = add_litlist(b, re->xl.prefixes.lits);
+      skip_ok = true;
+    }
+  }
   if (mt_lane) {
     lp = add_litlist(b, re->xl.prefixes.lits);
     ls = add_litlist(b, re->xl.suffixes.lits);
@@ -737,6 +763,18 @@ DevTables *regex_device(rure *re, std::string *err) {
     // a regex anchored at the end and not at the start runs the reverse DFA
     // from the end of the text (exec.rs:1175-1177, 671-688)
     t.anchored_rev = !re->nfa.anchored_start && re->nfa.anchored_end;
+  }
+  if (skip_ok) {
+    t.skip_on = true;
+    t.sk.f = FwdDfaDev{};
+    t.sk.f.full = (const uint16_t *)(base + o_kfull);
+    t.sk.f.eof = base + o_keof;
+    t.sk.f.start = (const uint16_t *)(base + o_kstart);
+    t.sk.f.n_normal = raw.n_normal;
+    t.sk.f.n_match_end = raw.n_match_end;
+    t.sk.f.dead = raw.dead;
+    t.sk.f.quit = raw.quit < 0 ? 0xFFFFFFFFu : (uint32_t)raw.quit;
+    t.sk.pre = LitListDev{base + lk.bytes, (const uint32_t *)(base + lk.off), lk.n, re->xl.prefixes.matcher};
   }
   t.owner = re;
   if (t.quit_possible && !re->nfa_ok) {

@@ -6,6 +6,7 @@
 // engine construction of src/exec.rs:273-327 (three programs per regex: NFA,
 // forward DFA with `.*?`, reverse DFA).  All matching runs on the GPU.
 #include "runtime.hpp"
+#include "host/expand.hpp"
 
 namespace {
 
@@ -815,6 +816,125 @@ int rure_amd_replace_batch(rure *re, const rure_amd_batch *batch, const uint8_t 
   if (shift) (void)scratch_free(shift, st);
   if (olen) (void)scratch_free(olen, st);
   if (drep) (void)scratch_free(drep, st);
+  return e == hipSuccess ? RURE_AMD_OK : RURE_AMD_ERR_HIP;
+}
+
+int rure_amd_captures_iter_batch(rure *re, const rure_amd_batch *batch, uint64_t *counts, size_t *slots,
+                                 size_t capacity, uint64_t *total, uint8_t *diverged, void *stream) {
+  static_assert(sizeof(size_t) == 8, "64-bit slots");
+  BatchDev b;
+  if (!re || !to_batch(batch, &b) || b.start != 0 || !total || (b.count && (!counts || !diverged)) ||
+      (!slots && capacity))
+    return RURE_AMD_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  if (b.count == 0) return hipMemsetAsync(total, 0, 8, st) == hipSuccess ? RURE_AMD_OK : RURE_AMD_ERR_HIP;
+  std::string err;
+  DevTables *t = regex_device(re, &err);
+  if (!t) return err.rfind("HIP", 0) == 0 ? RURE_AMD_ERR_HIP : RURE_AMD_ERR_DFA;
+  const uint32_t ns = capture_slots(re);
+  if (!re->nfa_ok && (ns > 2 || !t->has_dfa)) return RURE_AMD_ERR_DFA;
+  IterBufs ib;
+  uint64_t *tmp = nullptr;
+  hipError_t e = iter_to_device(re, t, b, st, &ib, &err);
+  if (e == hipSuccess) e = hipMemsetAsync(diverged, 0, b.count, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(counts, ib.counts, b.count * 8, hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(total, ib.total, 8, hipMemcpyDeviceToDevice, st);
+  const uint64_t nrows = std::min<uint64_t>(ib.nm, capacity);
+  if (e == hipSuccess && ns <= 2) {
+    // one group: the reference's captures are its plain find (exec.rs:533-541)
+    if (nrows) e = hipMemcpyAsync(slots, ib.m, nrows * 16, hipMemcpyDeviceToDevice, st);
+  } else if (e == hipSuccess && ib.nm) {
+    // every match is run (a short `slots` must not hide a divergence): into
+    // the caller's rows when they hold all of them, else into scratch
+    uint64_t *rows = (uint64_t *)slots;
+    if (ib.nm > capacity) {
+      e = scratch_malloc((void **)&tmp, ib.nm * ns * 8, st);
+      rows = tmp;
+    }
+    if (e == hipSuccess) e = run_captures_iter(b, *t, ib, ~0ull, rows, ns, diverged, st);
+    if (e == hipSuccess && tmp && nrows)
+      e = hipMemcpyAsync(slots, tmp, nrows * ns * 8, hipMemcpyDeviceToDevice, st);
+  }
+  if (tmp) (void)scratch_free(tmp, st);
+  if (e == hipSuccess) note_fwd_path(-28);
+  return e == hipSuccess ? RURE_AMD_OK : RURE_AMD_ERR_HIP;
+}
+
+long rure_amd_expand_template_export(rure *re, const uint8_t *rep, size_t rep_len, uint32_t *pieces, size_t cap,
+                                     uint8_t *lits, size_t lits_cap) {
+  if (!re || (!rep && rep_len)) return RURE_AMD_ERR_ARG;
+  if (!build_regex(re)) return RURE_AMD_ERR_DFA;
+  const Template tp = compile_template(rep, rep_len, re->nfa.capture_names, re->nfa.capture_has_name);
+  if (pieces)
+    for (size_t i = 0; i < std::min(cap, tp.pieces.size()); ++i) {
+      pieces[3 * i] = tp.pieces[i].kind;
+      pieces[3 * i + 1] = tp.pieces[i].a;
+      pieces[3 * i + 2] = tp.pieces[i].b;
+    }
+  if (lits) memcpy(lits, tp.lits.data(), std::min(lits_cap, tp.lits.size()));
+  return (long)tp.pieces.size();
+}
+
+int rure_amd_replace_expand_batch(rure *re, const rure_amd_batch *batch, const uint8_t *rep, size_t rep_len,
+                                  size_t limit, uint8_t *out, uint64_t *out_offsets, size_t out_capacity,
+                                  uint64_t *total, uint8_t *diverged, void *stream) {
+  BatchDev b;
+  if (!re || !to_batch(batch, &b) || b.start != 0 || !out_offsets || !total || (!out && out_capacity) ||
+      (!rep && rep_len) || (b.count && !diverged))
+    return RURE_AMD_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  if (b.count == 0) return hipMemsetAsync(out_offsets, 0, 8, st) == hipSuccess &&
+                           hipMemsetAsync(total, 0, 8, st) == hipSuccess ? RURE_AMD_OK : RURE_AMD_ERR_HIP;
+  std::string err;
+  DevTables *t = regex_device(re, &err);
+  if (!t) return err.rfind("HIP", 0) == 0 ? RURE_AMD_ERR_HIP : RURE_AMD_ERR_DFA;
+  const uint32_t ns = capture_slots(re);
+  if (!re->nfa_ok && (ns > 2 || !t->has_dfa)) return RURE_AMD_ERR_DFA;
+  const uint64_t lim = limit == 0 ? ~0ull : (uint64_t)limit;  // replacen: 0 = all
+  const Template tp = compile_template(rep, rep_len, re->nfa.capture_names, re->nfa.capture_has_name);
+  // Group 0 alone is the match list itself when the Pike VM's group 0 cannot
+  // differ from the DFA's bounds: one group (the reference's plain find), or
+  // a program without look-around (no thread can see the window's cut).
+  const bool need_caps = ns > 2 && (tp.names_groups || re->nt.looks_used != 0);
+  std::vector<uint32_t> hp(3 * tp.pieces.size() + 1, 0);
+  for (size_t i = 0; i < tp.pieces.size(); ++i) {
+    hp[3 * i] = tp.pieces[i].kind;
+    hp[3 * i + 1] = tp.pieces[i].a;
+    hp[3 * i + 2] = tp.pieces[i].b;
+  }
+  IterBufs ib;
+  uint64_t *rows = nullptr, *seg = nullptr, *S = nullptr, *olen = nullptr, *units = nullptr, *uoff = nullptr;
+  uint32_t *dp = nullptr;
+  uint8_t *dl = nullptr;
+  hipError_t e = iter_to_device(re, t, b, st, &ib, &err);
+  if (e == hipSuccess) e = hipMemsetAsync(diverged, 0, b.count, st);
+  if (e == hipSuccess && need_caps && ib.nm) e = scratch_malloc((void **)&rows, ib.nm * ns * 8, st);
+  if (e == hipSuccess) e = scratch_malloc((void **)&seg, (ib.nm + 1) * 8, st);
+  if (e == hipSuccess) e = scratch_malloc((void **)&S, (ib.nm + 1) * 8, st);
+  if (e == hipSuccess) e = scratch_malloc((void **)&olen, (b.count + 1) * 8, st);
+  if (e == hipSuccess && b.offs) e = scratch_malloc((void **)&units, (b.count + 1) * 8, st);
+  if (e == hipSuccess && b.offs) e = scratch_malloc((void **)&uoff, (b.count + 1) * 8, st);
+  if (e == hipSuccess) e = scratch_malloc((void **)&dp, hp.size() * 4, st);
+  if (e == hipSuccess) e = scratch_malloc((void **)&dl, std::max<size_t>(tp.lits.size(), 1), st);
+  if (e == hipSuccess) e = hipMemcpyAsync(dp, hp.data(), hp.size() * 4, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && !tp.lits.empty())
+    e = hipMemcpyAsync(dl, tp.lits.data(), tp.lits.size(), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && need_caps) e = run_captures_iter(b, *t, ib, lim, rows, ns, diverged, st);
+  const uint64_t *r = need_caps ? rows : ib.m;
+  const uint32_t rns = need_caps ? ns : 2;
+  const ExpandTpl dt{dp, (uint32_t)tp.pieces.size(), dl, tp.lits.size()};
+  if (e == hipSuccess)
+    e = launch_expand_plan(b, ib.counts, ib.moff, ib.m, ib.nm, lim, r, rns, dt, seg, S, olen, out_offsets, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(total, out_offsets + b.count, 8, hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess && out_capacity)
+    e = launch_expand_write(b, ib.counts, ib.moff, ib.m, ib.nm, lim, r, rns, dt, S, out_offsets, units, uoff, out,
+                            out_capacity, st, t->cus);
+  // the host copies above read hp / tp.lits, which die with this call
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  for (void *p : {(void *)rows, (void *)seg, (void *)S, (void *)olen, (void *)units, (void *)uoff, (void *)dp,
+                  (void *)dl})
+    if (p) (void)scratch_free(p, st);
+  if (e == hipSuccess) note_fwd_path(-29);
   return e == hipSuccess ? RURE_AMD_OK : RURE_AMD_ERR_HIP;
 }
 

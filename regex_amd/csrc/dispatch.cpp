@@ -345,9 +345,35 @@ hipError_t run_captures(const BatchDev &b, const DevTables &t, uint64_t *slots, 
   const int grid = (int)std::max<size_t>(1, g);
   void *scratch = nullptr;
   if (e == hipSuccess && !in_lds) e = scratch_malloc(&scratch, wb * (size_t)grid, st);
-  if (e == hipSuccess) e = launch_captures(b, t.n, found, slots, ns, scratch, st, grid);
+  if (e == hipSuccess)
+    e = launch_captures(b, t.n, found, slots, ns, scratch, found && t.skip_on && !lane_search_ok(t) ? &t.sk : nullptr,
+                        t.r, st, grid);
   if (scratch) { hipError_t e2 = scratch_free(scratch, st); if (e == hipSuccess) e = e2; }
   if (found) { hipError_t e2 = scratch_free(found, st); if (e == hipSuccess) e = e2; }
+  return e;
+}
+
+// captures_iter for a batch (re_trait.rs:243-273 over read_captures_at): the
+// captures Pike VM once per match of the batched find_iter's list, a wave
+// per match; row placement and grid as run_captures, with the matches in the
+// haystacks' place.
+hipError_t run_captures_iter(const BatchDev &b, const DevTables &t, const IterBufs &ib, uint64_t limit, uint64_t *rows,
+                             uint32_t ns, uint8_t *diverged, hipStream_t st) {
+  if (ib.nm == 0) return hipSuccess;
+  const size_t wb = caps_wave_bytes(t.n.nleaves, ns);
+  const bool in_lds = wb <= kNfaLdsMax;
+  const size_t per_cu = in_lds ? std::max<size_t>(1, std::min<size_t>(32, (160u * 1024u) / wb)) : 4;
+  size_t g = std::min<size_t>(ib.nm, (size_t)t.cus * per_cu);
+  if (!in_lds) g = std::min<size_t>(g, (256u << 20) / wb);
+  const int grid = (int)std::max<size_t>(1, g);
+  void *scratch = nullptr;
+  hipError_t e = hipSuccess;
+  if (!in_lds) e = scratch_malloc(&scratch, wb * (size_t)grid, st);
+  if (e == hipSuccess)
+    e = launch_captures_iter(b, t.n, ib.moff, ib.m, ib.nm, limit, rows, ns, diverged, scratch,
+                             t.has_dfa && t.quit_possible && !lane_search_ok(t) ? &t.f : nullptr,
+                             t.skip_on ? &t.sk : nullptr, t.r, st, grid);
+  if (scratch) { hipError_t e2 = scratch_free(scratch, st); if (e == hipSuccess) e = e2; }
   return e;
 }
 

@@ -184,6 +184,21 @@ struct MatchDev {
   uint32_t lcs_len;
 };
 
+// The forward DFA as the reference's lazy DFA walks it, for the one question
+// where the walk and not the language decides: whether a search quits.  A
+// regex with prefix literals jumps, whenever a step lands on the search's own
+// start state, to the next prefix occurrence (dfa.rs:700-711, 1032-1037), so
+// it never reads (never quits on, with a Unicode \b) the bytes in between.
+// "The start state" is a state identity (dfa.rs:1196-1244: the flags and the
+// instruction list), which minimisation loses: f holds the raw, unminimised
+// automaton (full / eof / start and the id bounds only; hot = all = ustart1 =
+// 0), whose start[flag index] is that state.  pre: dfa.prefixes (exec.rs:
+// 308-311).  Built only for a regex that needs it (DevTables::skip_on).
+struct SkipDfaDev {
+  FwdDfaDev f;
+  LitListDev pre;
+};
+
 struct RevDfaDev {
   const uint8_t *lds_image;   // hot table (same layout as FwdDfaDev::lds_image)
   uint32_t lds_bytes;
@@ -267,11 +282,49 @@ hipError_t launch_pike(int mode, bool fallback, const BatchDev &b, const NfaDev 
 // (start, end), NONE or the quit marker; null when every haystack is searched
 // whole from `start` (anchored-start programs).  slots: count x nslots u64,
 // NONE = unset.  Per-wave working set: caps_wave_bytes (LDS when it fits).
+// sk (or null) / r: where `found` holds the quit marker, the search is
+// repeated with the reference's start-state prefix skip (SkipDfaDev), which
+// may not quit: then its bounds cut the window as any DFA match's do.
 __host__ __device__ inline size_t caps_wave_bytes(uint32_t nleaves, uint32_t nslots) {
   return ((size_t)nleaves * (16 * (size_t)nslots + 12) + 64 + 255) & ~(size_t)255;
 }
 hipError_t launch_captures(const BatchDev &b, const NfaDev &n, const uint64_t *found, uint64_t *slots,
-                           uint32_t nslots, void *scratch, hipStream_t st, int grid);
+                           uint32_t nslots, void *scratch, const SkipDfaDev *sk, const RevDfaDev &r, hipStream_t st,
+                           int grid);
+
+// captures_iter over the batched find_iter's match list (nfa_scan.hip
+// caps_iter_kernel): moff (count + 1) / m (nm records) as below; row g of
+// `rows` (nslots u64, NONE = unset) = the groups of match g, for the matches
+// whose index within their haystack is below `limit`; diverged[h] (bytes,
+// zeroed by the caller) set where a row's group 0 is not its match.  fq / r:
+// the forward DFA when it can quit (else nullptr) and the reverse DFA, with
+// which a failing row repeats the reference's search (a quit there takes the
+// captures from the whole text); sk (or null): that search with the
+// reference's start-state prefix skip, in fq's place.  scratch and grid as
+// launch_captures.
+hipError_t launch_captures_iter(const BatchDev &b, const NfaDev &n, const uint64_t *moff, const uint64_t *m,
+                                uint64_t nm, uint64_t limit, uint64_t *rows, uint32_t nslots, uint8_t *diverged,
+                                void *scratch, const FwdDfaDev *fq, const SkipDfaDev *sk, const RevDfaDev &r,
+                                hipStream_t st, int grid);
+
+// replacen with a `$` template over find_iter output and captures_iter rows
+// (expand_scan.hip).  The compiled template (device): npieces records of 3
+// u32 (0, offset into lits, length) | (1, group, 0); lit_total = the sum of
+// the literal lengths.  seg / S: nm + 1 entries, olen: count + 1 (scratch);
+// units / uoff: count + 1 entries, used for offset batches only.
+struct ExpandTpl {
+  const uint32_t *pieces;
+  uint32_t npieces;
+  const uint8_t *lits;
+  uint64_t lit_total;
+};
+hipError_t launch_expand_plan(const BatchDev &b, const uint64_t *counts, const uint64_t *moff, const uint64_t *m,
+                              uint64_t nm, uint64_t limit, const uint64_t *rows, uint32_t ns, const ExpandTpl &tp,
+                              uint64_t *seg, uint64_t *S, uint64_t *olen, uint64_t *out_offsets, hipStream_t st);
+hipError_t launch_expand_write(const BatchDev &b, const uint64_t *counts, const uint64_t *moff, const uint64_t *m,
+                               uint64_t nm, uint64_t limit, const uint64_t *rows, uint32_t ns, const ExpandTpl &tp,
+                               const uint64_t *S, const uint64_t *out_offsets, uint64_t *units, uint64_t *uoff,
+                               uint8_t *out, uint64_t cap, hipStream_t st, int cus);
 
 // replacen / split over find_iter output (replace_scan.hip).  counts / moff:
 // matches per haystack and their exclusive sums; m: the records.

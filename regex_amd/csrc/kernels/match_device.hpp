@@ -83,6 +83,42 @@ __device__ __forceinline__ bool lits_find(const LitListDev &l, const uint8_t *ba
   return true;
 }
 
+// dfa_find as the reference's lazy DFA walks it (SkipDfaDev; dfa.rs:620-763
+// with has_prefix): the scan begins in the start state, and whenever it is in
+// that state (at first, and after any step that lands on it, dfa.rs:1032-1037)
+// it jumps to the next occurrence of a prefix literal, or ends with NoMatch
+// when there is none (dfa.rs:700-711).  One byte per step over the global
+// tables; the skipped bytes are never read, so they cannot quit.
+__device__ __forceinline__ int dfa_find_skip(const SkipDfaDev &k, const RevDfaDev &r, const uint8_t *base,
+                                             uint64_t len, uint64_t at, uint64_t *ms, uint64_t *me) {
+  LaneState L;
+  lane_start(L, k.f, base, len, at);
+  const uint32_t s0 = L.s;
+  bool in_start = true;
+  uint64_t pos = at;
+  while (!L.done && pos < len) {
+    if (in_start) {
+      uint64_t a, b;
+      if (!lits_find(k.pre, base, len, pos, &a, &b)) return 0;
+      pos = a;
+      if (pos >= len) break;
+    }
+    careful_step<MODE_FIND>(L, k.f, base[pos], pos);
+    ++pos;
+    in_start = L.s == s0;
+  }
+  if (!L.done && k.f.eof[L.s]) L.last = len;
+  if (L.quit) return 2;
+  if (L.last == NONE) return 0;
+  *me = L.last;
+  if (L.last == at) { *ms = at; return 1; }  // exec.rs:647
+  const uint64_t rs = rev_scan(r, nullptr, base, len, at, L.last);
+  if (rs == QUITMARK) return 2;
+  if (rs == NONE) return 0;
+  *ms = rs;
+  return 1;
+}
+
 // find_start / find_end (literals.rs:105-128)
 __device__ __forceinline__ bool lits_find_start(const LitListDev &l, const uint8_t *base, uint64_t len,
                                                 uint64_t at, uint64_t *ms, uint64_t *me) {

@@ -102,6 +102,10 @@ struct DevTables {
   MatchDev m{-1, {}, {}, nullptr, 0};
   bool mt_lane = false;
   bool lcs_free = false;    // DfaSuffix: the longest common suffix cannot overlap itself (launch_suffix_long)
+  // The reference's walk of the forward DFA with its start-state prefix skip
+  // (SkipDfaDev), where it decides a quit that the captures depend on
+  bool skip_on = false;
+  SkipDfaDev sk{};
   int cus = 256;
 };
 
@@ -375,6 +379,8 @@ hipError_t run_regex(int mode, const BatchDev &b, const DevTables &t, void *out,
 hipError_t run_set(const BatchDev &b, const DevTables &t, uint64_t *out, hipStream_t st, int dfa_grid);
 hipError_t run_captures(const BatchDev &b, const DevTables &t, uint64_t *slots, uint32_t ns, hipStream_t st,
                         int dfa_grid);
+hipError_t run_captures_iter(const BatchDev &b, const DevTables &t, const IterBufs &ib, uint64_t limit, uint64_t *rows,
+                             uint32_t ns, uint8_t *diverged, hipStream_t st);
 bool to_batch(const rure_amd_batch *b, BatchDev *o);
 bool single_call(rure *re, int mode, const uint8_t *hay, size_t len, size_t start, uint64_t *r0, uint64_t *r1);
 uint64_t set_single_call(rure_set *rs, const uint8_t *hay, size_t len, size_t start);
