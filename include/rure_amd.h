@@ -221,7 +221,7 @@ int rure_amd_replace_batch(rure *re, const rure_amd_batch *batch, const uint8_t 
  * over a regex without look-around, and any template over a regex without
  * groups, skip the captures pass (diverged stays 0).  Synchronises the stream
  * to size the match buffer and once more before it returns.
- * rure_amd_last_fwd_path: -29. */
+ * rure_amd_last_fwd_path: RURE_AMD_PATH_REPLACE_EXPAND. */
 int rure_amd_replace_expand_batch(rure *re, const rure_amd_batch *batch, const uint8_t *rep, size_t rep_len,
                                   size_t limit, uint8_t *out, uint64_t *out_offsets, size_t out_capacity,
                                   uint64_t *total, uint8_t *diverged, void *stream);
@@ -310,7 +310,7 @@ size_t rure_amd_captures_len(rure *re);
  * Synchronisation as for
  * rure_amd_find_iter_batch's internal use by rure_amd_replace_batch: once to
  * size the match buffer (twice if the first guess was short).
- * rure_amd_last_fwd_path: -28. */
+ * rure_amd_last_fwd_path: RURE_AMD_PATH_CAPTURES_ITER. */
 int rure_amd_captures_iter_batch(rure *re, const rure_amd_batch *batch, uint64_t *counts, size_t *slots,
                                  size_t capacity, uint64_t *total, uint8_t *diverged, void *stream);
 
@@ -426,7 +426,8 @@ int rure_amd_run_class_export(rure *re, int ascii, uint8_t *cls);
 int rure_amd_run_cp_export(rure *re, uint32_t *bits, size_t n);
 /* 1 if every match of the regex is exactly one byte of a class (cls[b] = 1
  * for its bytes): its replace_all over one haystack then runs without a
- * match list (rure_amd_replace_batch, last_fwd_path -23); 0 if not. */
+ * match list (rure_amd_replace_batch, RURE_AMD_PATH_REPLACE_CLASS); 0 if
+ * not. */
 int rure_amd_class_one_export(rure *re, uint8_t *cls);
 
 /* Export of the Pike VM closure tables the NFA kernel runs (host only):
@@ -490,25 +491,43 @@ int rure_amd_match_info_get(rure *re, rure_amd_match_info *info);
  * Pike VM kernel (automaton too large), negative on error. */
 int rure_amd_uses_dfa(rure *re);
 int rure_amd_set_uses_dfa(rure_set *re);
-/* Diagnostics (host only): the scan engine the last batched launch of this
- * process used — 0 = the per-lane streaming kernel, 1 / 2 / 4 = the
- * coalesced-tile kernel with that many bytes per dependent table lookup,
- * -2 = the reverse DFA from the end (DfaAnchoredReverse), -3 = the literal
- * engine (MatchType::Literal), -4 = the chunked cut-bounded scan (long
- * haystacks, small batches split into units), -5 = the lane search of the
- * Literal / DfaSuffix match types, -6 = the big (u32) DFA, (-7: unused
- * since round 5), -8 = the ragged line kernel, -9 = the
- * chunked DfaSuffix scan, -10 = the on-demand DFA, -11 = the DfaSuffix
- * find_iter, -12 / -13 = the chunked find_iter of a look-around regex (no
- * quit / a quit sent it to the wave path), -14 / -15 = the ASCII-shadow
- * find_iter (answered / quit), -16 = the Pike VM alone (no DFA), -17 = the
- * core-form set kernel over an offset batch, -19 / -20 = the find_iter run
- * engine of a C+ regex (its class over all bytes / the ASCII shadow's),
- * -21 = the chunked find_iter of the full automaton (no look-around), -22 =
- * find_iter with one haystack per wavefront, -23 = replace_all of a
- * one-byte-class regex without a match list, -28 = the batched captures_iter
- * (a wave per match), -29 = the batched replacen with a `$` template; -1
- * before the first launch. */
+/* Diagnostics (host only): the engine that answered a batched call.  The
+ * values are frozen (recorded profiles hold them); a new engine takes a new
+ * value. */
+typedef enum rure_amd_path {
+  RURE_AMD_PATH_NONE = -1,              /* before the first launch */
+  RURE_AMD_PATH_LANE_STREAM = 0,        /* the per-lane streaming kernel */
+  RURE_AMD_PATH_TILE1 = 1,              /* the coalesced-tile kernel, 1 byte per dependent table lookup */
+  RURE_AMD_PATH_TILE2 = 2,              /* the coalesced-tile kernel, 2 bytes per lookup */
+  RURE_AMD_PATH_TILE4 = 4,              /* the coalesced-tile kernel, 4 bytes per lookup */
+  RURE_AMD_PATH_ANCHORED_REVERSE = -2,  /* the reverse DFA from the end (DfaAnchoredReverse) */
+  RURE_AMD_PATH_LITERAL = -3,           /* the literal engine (MatchType::Literal) */
+  RURE_AMD_PATH_LONG_SCAN = -4,         /* the chunked cut-bounded scan (long haystacks split into units) */
+  RURE_AMD_PATH_LANE_SEARCH = -5,       /* the lane search of the Literal / DfaSuffix match types */
+  RURE_AMD_PATH_BIG_DFA = -6,           /* the big (u32) DFA */
+  RURE_AMD_PATH_LINES = -8,             /* the ragged line kernel */
+  RURE_AMD_PATH_SUFFIX_LONG = -9,       /* the chunked DfaSuffix scan */
+  RURE_AMD_PATH_LAZY_DFA = -10,         /* the on-demand DFA */
+  RURE_AMD_PATH_SUFFIX_ITER = -11,      /* the DfaSuffix find_iter */
+  RURE_AMD_PATH_ITER_LOOKS = -12,       /* the chunked find_iter of a look-around regex answered */
+  RURE_AMD_PATH_ITER_LOOKS_QUIT = -13,  /* it quit: one haystack per wavefront answers */
+  RURE_AMD_PATH_ITER_SHADOW = -14,      /* the find_iter ASCII shadow answered, its quit read back */
+  RURE_AMD_PATH_ITER_SHADOW_QUIT = -15, /* it quit, and the full automaton re-ran the batch, chunked */
+  RURE_AMD_PATH_PIKE_ONLY = -16,        /* the Pike VM alone (no DFA) */
+  RURE_AMD_PATH_SET_CORE_OFFSETS = -17, /* the core-form set kernel over an offset batch */
+  RURE_AMD_PATH_ITER_RUNS = -19,        /* the find_iter run engine of a C+ regex, its class over all bytes */
+  RURE_AMD_PATH_ITER_RUNS_ASCII = -20,  /* the run engine with the ASCII shadow's class */
+  RURE_AMD_PATH_ITER_CHUNKED = -21,     /* the chunked find_iter of the full automaton (no look-around) */
+  RURE_AMD_PATH_ITER_WAVE = -22,        /* find_iter with one haystack per wavefront */
+  RURE_AMD_PATH_REPLACE_CLASS = -23,    /* replace_all of a one-byte-class regex without a match list; a chain step by step */
+  RURE_AMD_PATH_REPLACE_HMAP = -24,     /* a replace_all chain as one composed byte map */
+  RURE_AMD_PATH_ITER_SHADOW_GATED = -25, /* shadow and full automaton both enqueued, the quit kept on the device */
+  RURE_AMD_PATH_ITER_WAVE_SERVED = -27, /* chunked find_iter whose quitting units are served by waves */
+  RURE_AMD_PATH_CAPTURES_ITER = -28,    /* the batched captures_iter (a wave per match) */
+  RURE_AMD_PATH_REPLACE_EXPAND = -29    /* the batched replacen with a `$` template */
+} rure_amd_path;
+/* The rure_amd_path of the last batched launch of this process (one value
+ * for the whole process, not per thread or stream). */
 int rure_amd_last_fwd_path(void);
 /* Debug-only overrides of the engine dispatch and launch geometry
  * (regex_amd/csrc/host/knobs.hpp lists them): replaces the whole override

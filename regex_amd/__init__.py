@@ -15,9 +15,10 @@ import ctypes
 
 from . import _native as N
 
-__all__ = ["Regex", "RegexSet", "Error", "NoExpand", "NONE", "release_scratch"]
+__all__ = ["Regex", "RegexSet", "Error", "NoExpand", "NONE", "Path", "release_scratch"]
 
 NONE = N.NONE
+Path = N.Path
 
 
 def _ser_lits(lits):

@@ -5,6 +5,7 @@ regex_amd/lib/.  There is no fallback: if the shared object is missing the
 import fails loudly.
 """
 import ctypes
+import enum
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -160,6 +161,47 @@ rure_amd_shiftand_export = _sig("rure_amd_shiftand_export", ctypes.c_int64, VP, 
 rure_amd_uses_dfa = _sig("rure_amd_uses_dfa", ctypes.c_int, VP)
 rure_amd_set_uses_dfa = _sig("rure_amd_set_uses_dfa", ctypes.c_int, VP)
 rure_amd_last_fwd_path = _sig("rure_amd_last_fwd_path", ctypes.c_int)
+
+
+class Path(enum.IntEnum):
+    """rure_amd_path (include/rure_amd.h, which says what each one means)."""
+    NONE = -1
+    LANE_STREAM = 0
+    TILE1 = 1
+    TILE2 = 2
+    TILE4 = 4
+    ANCHORED_REVERSE = -2
+    LITERAL = -3
+    LONG_SCAN = -4
+    LANE_SEARCH = -5
+    BIG_DFA = -6
+    LINES = -8
+    SUFFIX_LONG = -9
+    LAZY_DFA = -10
+    SUFFIX_ITER = -11
+    ITER_LOOKS = -12
+    ITER_LOOKS_QUIT = -13
+    ITER_SHADOW = -14
+    ITER_SHADOW_QUIT = -15
+    PIKE_ONLY = -16
+    SET_CORE_OFFSETS = -17
+    ITER_RUNS = -19
+    ITER_RUNS_ASCII = -20
+    ITER_CHUNKED = -21
+    ITER_WAVE = -22
+    REPLACE_CLASS = -23
+    REPLACE_HMAP = -24
+    ITER_SHADOW_GATED = -25
+    ITER_WAVE_SERVED = -27
+    CAPTURES_ITER = -28
+    REPLACE_EXPAND = -29
+
+
+def last_path():
+    """The engine that answered the last batched launch of this process."""
+    return Path(rure_amd_last_fwd_path())
+
+
 rure_amd_debug_set = _sig("rure_amd_debug_set", ctypes.c_int, ctypes.c_char_p)
 rure_amd_first_byte_export = _sig("rure_amd_first_byte_export", ctypes.c_int, VP, VP)
 rure_amd_lex_export = _sig("rure_amd_lex_export", ctypes.c_int64, VP, VP, c_size, VP)

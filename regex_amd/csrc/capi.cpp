@@ -730,7 +730,7 @@ int rure_amd_replace_all_chain(rure *const *res, const uint8_t *const *reps, con
         e = launch_replace_hmap(haystack, length, (int)n, db, (uint32_t)pool, nact, out, capacity, lengths, st,
                                 cus);
       if (db) { const hipError_t e2 = scratch_free(db, st); if (e == hipSuccess) e = e2; }
-      if (e == hipSuccess) note_fwd_path(-24);
+      if (e == hipSuccess) note_fwd_path(RURE_AMD_PATH_REPLACE_HMAP);
       if (e != hipErrorNotSupported) return e == hipSuccess ? RURE_AMD_OK : RURE_AMD_ERR_HIP;
     }
   }
@@ -753,7 +753,7 @@ int rure_amd_replace_all_chain(rure *const *res, const uint8_t *const *reps, con
   }
   if (dt) { const hipError_t e2 = scratch_free(dt, st); if (e == hipSuccess) e = e2; }
   if (e == hipErrorNotSupported) return RURE_AMD_ERR_ARG;
-  if (e == hipSuccess) note_fwd_path(-23);
+  if (e == hipSuccess) note_fwd_path(RURE_AMD_PATH_REPLACE_CLASS);
   return e == hipSuccess ? RURE_AMD_OK : RURE_AMD_ERR_HIP;
 }
 
@@ -790,7 +790,7 @@ int rure_amd_replace_batch(rure *re, const rure_amd_batch *batch, const uint8_t 
                                st, t->cus, sw[0], sw[1]);
     if (dt) { const hipError_t e2 = scratch_free(dt, st); if (e == hipSuccess) e = e2; }
     if (e != hipErrorNotSupported) {
-      if (e == hipSuccess) note_fwd_path(-23);
+      if (e == hipSuccess) note_fwd_path(RURE_AMD_PATH_REPLACE_CLASS);
       return e == hipSuccess ? RURE_AMD_OK : RURE_AMD_ERR_HIP;
     }
   }
@@ -856,7 +856,7 @@ int rure_amd_captures_iter_batch(rure *re, const rure_amd_batch *batch, uint64_t
       e = hipMemcpyAsync(slots, tmp, nrows * ns * 8, hipMemcpyDeviceToDevice, st);
   }
   if (tmp) (void)scratch_free(tmp, st);
-  if (e == hipSuccess) note_fwd_path(-28);
+  if (e == hipSuccess) note_fwd_path(RURE_AMD_PATH_CAPTURES_ITER);
   return e == hipSuccess ? RURE_AMD_OK : RURE_AMD_ERR_HIP;
 }
 
@@ -934,7 +934,7 @@ int rure_amd_replace_expand_batch(rure *re, const rure_amd_batch *batch, const u
   for (void *p : {(void *)rows, (void *)seg, (void *)S, (void *)olen, (void *)units, (void *)uoff, (void *)dp,
                   (void *)dl})
     if (p) (void)scratch_free(p, st);
-  if (e == hipSuccess) note_fwd_path(-29);
+  if (e == hipSuccess) note_fwd_path(RURE_AMD_PATH_REPLACE_EXPAND);
   return e == hipSuccess ? RURE_AMD_OK : RURE_AMD_ERR_HIP;
 }
 

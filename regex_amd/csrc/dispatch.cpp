@@ -4,6 +4,15 @@
 // passes and the k-mer table cache.
 #include "runtime.hpp"
 
+namespace rure_amd {
+
+// rure_amd_last_fwd_path: one value for the whole process, touched only here.
+static std::atomic<int> g_last_fwd_path{RURE_AMD_PATH_NONE};
+int last_fwd_path() { return g_last_fwd_path.load(); }
+void note_fwd_path(rure_amd_path path) { g_last_fwd_path.store(path); }
+
+}  // namespace rure_amd
+
 namespace rt {
 
 int device_cus(int dev) {
@@ -33,7 +42,7 @@ int pike_grid(size_t count, bool fallback, const NfaDev &n, int cus) {
 
 // Pike VM pass: all haystacks (no DFA) or only those the DFA quit on.
 hipError_t run_pike(int mode, bool fallback, const BatchDev &b, const DevTables &t, void *out, hipStream_t st) {
-  if (!fallback) note_fwd_path(-16);
+  if (!fallback) note_fwd_path(RURE_AMD_PATH_PIKE_ONLY);
   int grid = pike_grid(b.count, fallback, t.n, t.cus);
   size_t wb = nfa_wave_bytes(t.n.nleaves);
   if (wb <= kNfaLdsMax) return launch_pike(mode, fallback, b, t.n, out, nullptr, st, grid);
@@ -565,6 +574,7 @@ hipError_t run_find_iter(rure *re, DevTables *t, const BatchDev &b, const IterOu
   const bool looks = re->nt.looks_used != 0 || t->quit_possible;
   if (t->has_dfa && re->nfa_ok && (!looks || (!sp && knob(Knob::IterLooks) != 0))) fi = iter_device(re, *t, err);
   if (fi && looks && re->dfwd_iter.strip.empty()) fi = nullptr;
+  bool looks_quit = false;  // the chunked pass of a look-around regex quit
   if (fi) {
     uint64_t chunk = ~0ull >> 2;
     const uint64_t lim = sp ? std::min<uint64_t>(b.length, sp->hi) : b.length;
@@ -591,7 +601,7 @@ hipError_t run_find_iter(rure *re, DevTables *t, const BatchDev &b, const IterOu
       bool q = false;
       const hipError_t e = launch_find_iter_runs(b, fi->run_cls, fi->run_cp, o, st, t->cus, fi->run_quit != 0, &q);
       if (e != hipErrorNotSupported && (e != hipSuccess || !q)) {
-        if (e == hipSuccess) note_fwd_path(-19);
+        if (e == hipSuccess) note_fwd_path(RURE_AMD_PATH_ITER_RUNS);
         return e;
       }
       run_quit = q;
@@ -607,15 +617,15 @@ hipError_t run_find_iter(rure *re, DevTables *t, const BatchDev &b, const IterOu
           bool q = false;
           const hipError_t e = launch_find_iter_runs(b, fa->run_cls, nullptr, o, st, t->cus, true, &q);
           if (e != hipErrorNotSupported && (e != hipSuccess || !q)) {
-            if (e == hipSuccess) note_fwd_path(-20);
+            if (e == hipSuccess) note_fwd_path(RURE_AMD_PATH_ITER_RUNS_ASCII);
             return e;
           }
         }
         // The full automaton cannot quit: both passes are enqueued, the
         // shadow's quit staying a device word -- its passes after the quit
         // check run while the word is 0, the full automaton's while it is set
-        // (-25; nothing read back, the call only enqueues).  Knob
-        // shadow_sync=1 reads the quit back (-14 / -15).
+        // (nothing read back, the call only enqueues).  Knob shadow_sync=1
+        // reads the quit back.
         if (!fi->can_quit && knob(Knob::ShadowSync) != 1) {
           uint32_t *qf = nullptr;
           hipError_t e = scratch_malloc((void **)&qf, 8, st);
@@ -632,40 +642,43 @@ hipError_t run_find_iter(rure *re, DevTables *t, const BatchDev &b, const IterOu
             const hipError_t e2 = scratch_free(qf, st);
             if (e == hipSuccess) e = e2;
           }
-          if (e == hipSuccess) note_fwd_path(-25);
+          if (e == hipSuccess) note_fwd_path(RURE_AMD_PATH_ITER_SHADOW_GATED);
           return e;
         }
         bool q = false;
         const hipError_t e = launch_find_iter_chunked(b, *fa, t->r, chunk, o, st, t->cus, IterQuit::read_back(&q));
         if (e != hipSuccess || !q) {
-          if (e == hipSuccess) note_fwd_path(-14);
+          if (e == hipSuccess) note_fwd_path(RURE_AMD_PATH_ITER_SHADOW);
           return e;
         }
-        shadow_quit = true;  // a quit: the full automaton below answers (-15)
+        shadow_quit = true;  // a quit: the full automaton below answers
       }
     }
     // A DFA that can quit (Unicode \b over non-ASCII bytes): the units whose
     // searches quit are served by the wave's Pike VM inside the chunked
-    // iteration (iter_scan.hip iter_wspec_kernel .. iter_wemit_kernel; -27,
+    // iteration (iter_scan.hip iter_wspec_kernel .. iter_wemit_kernel;
     // nothing read back).  Spans, and knob iter_wave=0, keep the read-back of
-    // the quit and the one-wave-per-haystack fallback (-13).
+    // the quit and the one-wave-per-haystack fallback.
     if (fi->can_quit && !sp && re->nfa_ok && knob(Knob::IterWave) != 0) {
       const hipError_t e = launch_find_iter_chunked(b, *fi, t->r, chunk, o, st, t->cus, IterQuit::wave_served(&t->n));
-      if (e == hipSuccess) note_fwd_path(-27);
+      if (e == hipSuccess) note_fwd_path(RURE_AMD_PATH_ITER_WAVE_SERVED);
       return e;
     }
     bool quit = false;
     const hipError_t e = launch_find_iter_chunked(b, *fi, t->r, chunk, o, st, t->cus, IterQuit::read_back(&quit), sp);
-    // last_fwd_path: -12 = the chunked iteration of a look-around regex
-    // answered, -13 = it quit (the wave path answers)
-    // (-21: the chunked iteration of the full automaton answered; -15: so,
-    // after the ASCII shadow quit)
-    if (e == hipSuccess) note_fwd_path(looks ? (quit ? -13 : -12) : shadow_quit ? -15 : -21);
+    if (e == hipSuccess) {
+      if (looks)
+        note_fwd_path(quit ? RURE_AMD_PATH_ITER_LOOKS_QUIT : RURE_AMD_PATH_ITER_LOOKS);
+      else
+        note_fwd_path(shadow_quit ? RURE_AMD_PATH_ITER_SHADOW_QUIT : RURE_AMD_PATH_ITER_CHUNKED);
+    }
     if (e != hipSuccess || !quit) return e;
+    looks_quit = looks;
   }
   if (!re->nfa_ok) return hipErrorInvalidValue;
   const hipError_t e = launch_find_iter_wave(b, t->has_dfa ? &t->f : nullptr, t->r, t->n, o, st, t->cus, sp);
-  if (e == hipSuccess && last_fwd_path() != -13) note_fwd_path(-22);  // one haystack per wavefront
+  // after a look-around regex's quit, ITER_LOOKS_QUIT stands for the pair
+  if (e == hipSuccess && !looks_quit) note_fwd_path(RURE_AMD_PATH_ITER_WAVE);
   return e;
 }
 

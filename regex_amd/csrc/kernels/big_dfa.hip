@@ -263,7 +263,7 @@ hipError_t launch_lazy_dfa(int mode, const BatchDev &b, const LazyDfaDev &f, con
                            uint64_t nin, LazyPark *park, unsigned long long *npark, void *out, hipStream_t st,
                            int cus) {
   if (b.count == 0 || (in && nin == 0)) return hipSuccess;
-  note_fwd_path(-10);
+  note_fwd_path(RURE_AMD_PATH_LAZY_DFA);
   switch (mode) {
     case MODE_FIND: return launch_lazy_m<MODE_FIND>(b, f, r, in, nin, park, npark, out, st, cus);
     case MODE_ISMATCH: return launch_lazy_m<MODE_ISMATCH>(b, f, r, in, nin, park, npark, out, st, cus);
@@ -280,7 +280,7 @@ uint32_t big_dfa_hot_rows(uint32_t ncol, uint32_t nstates) {
 hipError_t launch_big_dfa(int mode, const BatchDev &b, const BigDfaDev &f, const BigDfaDev &r, void *out,
                           hipStream_t st, int cus) {
   if (b.count == 0) return hipSuccess;
-  note_fwd_path(-6);
+  note_fwd_path(RURE_AMD_PATH_BIG_DFA);
   switch (mode) {
     case MODE_FIND: return launch_big_m<MODE_FIND>(b, f, r, out, st, cus);
     case MODE_ISMATCH: return launch_big_m<MODE_ISMATCH>(b, f, r, out, st, cus);

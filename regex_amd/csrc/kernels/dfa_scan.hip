@@ -23,7 +23,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <atomic>
 #include <algorithm>
 #include <cstdlib>
 #include <mutex>
@@ -94,10 +93,6 @@ __global__ __launch_bounds__(256) void dfa_fwd_kernel(BatchDev bt, FwdDfaDev f, 
     finish_lane<MODE>(L, r, base, len, bt.start, h, out, bt.quit_flag);
   }
 }
-
-static std::atomic<int> g_last_fwd_path{-1};
-int last_fwd_path() { return g_last_fwd_path.load(); }
-void note_fwd_path(int path) { g_last_fwd_path.store(path); }
 
 // Kernel timer (bench diagnostics, rure_amd_kernel_timer): while on, the
 // launches a caller brackets with ktimer_begin / ktimer_end (the find_iter
@@ -238,7 +233,7 @@ hipError_t launch_lit_find(int mode, const BatchDev &b, const FwdDfaDev &f, void
   if (!f.lit_n || (mode != MODE_FIND && mode != MODE_ISMATCH)) return hipErrorInvalidValue;
   const uint64_t blocks = (b.count + 255) / 256;
   const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)f.cus * 32));
-  g_last_fwd_path.store(-3);
+  note_fwd_path(RURE_AMD_PATH_LITERAL);
   const bool strided = b.offs == nullptr;
   if (mode == MODE_FIND)
     return strided ? launch_lit_find_m<MODE_FIND, true>(b, f, out, st, grid)
@@ -837,7 +832,7 @@ hipError_t launch_set_cores(const BatchDev &b, const SetCoreDev &f, uint64_t *ou
             sum[0] / nw, sum[1] / nw, sum[2] / nw, sum[3] / nw, sum[4] / nw);
     return hipSuccess;
   }
-  if (mode == 1) note_fwd_path(-17);
+  if (mode == 1) note_fwd_path(RURE_AMD_PATH_SET_CORE_OFFSETS);
   if (mode == 1) return go(set_core_kernel<1>);
   return go(set_core_kernel<0>);
 }
@@ -1046,7 +1041,7 @@ static hipError_t launch_anchored_rev_m(const BatchDev &b, const RevDfaDev &r, v
 
 hipError_t launch_dfa_anchored_rev(int mode, const BatchDev &b, const RevDfaDev &r, void *out, hipStream_t st,
                                    int grid) {
-  g_last_fwd_path.store(-2);
+  note_fwd_path(RURE_AMD_PATH_ANCHORED_REVERSE);
   switch (mode) {
     case MODE_FIND: return launch_anchored_rev_m<MODE_FIND>(b, r, out, st, grid);
     case MODE_ISMATCH: return launch_anchored_rev_m<MODE_ISMATCH>(b, r, out, st, grid);
@@ -1070,7 +1065,11 @@ template <int MODE, int STRIDE>
 static hipError_t launch_tile_s(const BatchDev &b, const FwdDfaDev &f, const RevDfaDev &r, void *out, hipStream_t st,
                                 int grid) {
   const uint32_t bytes = STRIDE == 1 ? f.lds_bytes : f.lds_bytes_s;
-  g_last_fwd_path.store(STRIDE);
+  static_assert(RURE_AMD_PATH_TILE1 == 1 && RURE_AMD_PATH_TILE2 == 2 && RURE_AMD_PATH_TILE4 == 4,
+                "the tile paths are numbered by their stride");
+  constexpr rure_amd_path kPath =
+      STRIDE == 4 ? RURE_AMD_PATH_TILE4 : STRIDE == 2 ? RURE_AMD_PATH_TILE2 : RURE_AMD_PATH_TILE1;
+  note_fwd_path(kPath);
   // group scatter multiplier: a prime, coprime with the group count
   const uint64_t ngroups = (b.count + 63) / 64;
   uint64_t mul = 40503;
@@ -1122,14 +1121,14 @@ hipError_t launch_dfa_fwd(int mode, const BatchDev &b, const FwdDfaDev &f, const
     }
   }
   if (line_path_ok(b, f)) {
-    g_last_fwd_path.store(-8);
+    note_fwd_path(RURE_AMD_PATH_LINES);
     switch (mode) {
       case MODE_FIND: return launch_lines_m<MODE_FIND>(b, f, r, out, st);
       case MODE_ISMATCH: return launch_lines_m<MODE_ISMATCH>(b, f, r, out, st);
       default: return launch_lines_m<MODE_SHORTEST>(b, f, r, out, st);
     }
   }
-  g_last_fwd_path.store(0);
+  note_fwd_path(RURE_AMD_PATH_LANE_STREAM);
   switch (mode) {
     case MODE_FIND: return strided ? launch_fwd<MODE_FIND, true>(b, f, r, out, st, grid)
                                    : launch_fwd<MODE_FIND, false>(b, f, r, out, st, grid);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../../include/rure_amd.h"
 #include "../host/knobs.hpp"
 
 namespace rure_amd {
@@ -468,8 +469,7 @@ hipError_t launch_dfa_fwd(int mode, const BatchDev &b, const FwdDfaDev &f, const
 // find / is_match / shortest_match of a batch under the reference's Literal
 // or DfaSuffix match type (match_types.hip): one lane per haystack, global
 // DFA tables for DfaSuffix's reverse / forward scans; same output layout and
-// quit markers as launch_dfa_fwd (the Pike VM pass resolves quits);
-// last_fwd_path() = -5.
+// quit markers as launch_dfa_fwd (the Pike VM pass resolves quits).
 hipError_t launch_lane_search(int mode, const BatchDev &b, const MatchDev &m, const FwdDfaDev &f,
                               const RevDfaDev &r, void *out, hipStream_t st, int cus);
 // DfaSuffix over few long fixed-stride haystacks (match_types.hip): answers
@@ -488,15 +488,13 @@ hipError_t launch_suffix_long(int mode, const BatchDev &b, const MatchDev &m, co
                               int cus);
 // MatchType::Literal (exec.rs:601-625, 1148-1166) for MODE_FIND / MODE_ISMATCH
 // batches of a regex that is a finite string set: f = the find_iter DFA
-// (lit_n > 0); same output layout as launch_dfa_fwd; last_fwd_path() = -3.
+// (lit_n > 0); same output layout as launch_dfa_fwd.
 hipError_t launch_lit_find(int mode, const BatchDev &b, const FwdDfaDev &f, void *out, hipStream_t st);
-// Which forward-scan kernel the last launch_dfa_fwd call launched (tests
-// assert the instantiation the bench times): 0 = dfa_fwd_kernel (per-lane
-// streaming), 1 / 2 / 4 = dfa_fwd_tile_kernel with that many bytes per
-// dependent LDS lookup, -2 = the anchored reverse scan, -3 = the literal
-// engine, -4 = the chunked long scan (launch_long_scan).
+// Which engine answered the last batched launch of this process
+// (rure_amd_last_fwd_path; dispatch.cpp): the launchers and the dispatch note
+// it, tests and the bench assert it.
 int last_fwd_path();
-void note_fwd_path(int path);
+void note_fwd_path(rure_amd_path path);
 // Kernel timer (rure_amd_kernel_timer): HIP event pairs around bracketed launches.
 void ktimer_begin(hipStream_t st);
 void ktimer_end(hipStream_t st);

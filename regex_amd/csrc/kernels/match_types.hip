@@ -181,7 +181,7 @@ __global__ __launch_bounds__(256) void suffix_finish_kernel(BatchDev b, FwdDfaDe
 hipError_t launch_suffix_long(int mode, const BatchDev &b, const MatchDev &m, const FwdDfaDev &f,
                               const RevDfaDev &r, uint64_t chunk, void *out, uint8_t *status, hipStream_t st,
                               int cus) {
-  note_fwd_path(-9);
+  note_fwd_path(RURE_AMD_PATH_SUFFIX_LONG);
   FwdDfaDev fg = global_tables(f);  // global-table stepping
   fg.all = 0;
   fg.stride = 1;
@@ -233,7 +233,7 @@ hipError_t launch_suffix_long(int mode, const BatchDev &b, const MatchDev &m, co
 
 hipError_t launch_lane_search(int mode, const BatchDev &b, const MatchDev &m, const FwdDfaDev &f,
                               const RevDfaDev &r, void *out, hipStream_t st, int cus) {
-  note_fwd_path(-5);
+  note_fwd_path(RURE_AMD_PATH_LANE_SEARCH);
   FwdDfaDev fg = global_tables(f);  // global-table stepping (no LDS image staged)
   fg.all = 0;
   fg.stride = 1;
@@ -541,7 +541,7 @@ hipError_t launch_suffix_iter(const BatchDev &b, const MatchDev &m, const FwdDfa
   if (N) hipLaunchKernelGGL(suf_write_kernel, dim3(grid(N)), dim3(256), 0, st, N, flag, pos, ms, me, o.matches, o.cap);
   hipLaunchKernelGGL(suf_counts_kernel, dim3(grid(b.count + 1)), dim3(256), 0, st, b.count, hfirst, pos, o.counts,
                      o.total);
-  note_fwd_path(-11);
+  note_fwd_path(RURE_AMD_PATH_SUFFIX_ITER);
   return done(hipGetLastError());
 }
 

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import regex_amd as R
+from regex_amd import Path
 from regex_amd import _native as N
 from oracle_py import OracleRegex
 from regex_amd.workloads import date_haystacks_host, log_lines_host
@@ -50,7 +51,7 @@ def test_anchored_reverse_batch(cuda, pat, start):
     hay, offs = _ragged(texts, cuda)
     got = re.find_batch(hay, offsets=offs, start=start).cpu().numpy()
     if re.uses_dfa():
-        assert N.rure_amd_last_fwd_path() == -2
+        assert N.last_path() == Path.ANCHORED_REVERSE
     ism = re.is_match_batch(hay, offsets=offs, start=start).cpu().numpy()
     sho = re.shortest_match_batch(hay, offsets=offs, start=start).cpu().numpy()
     for i, t in enumerate(texts):

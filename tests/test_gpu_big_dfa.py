@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import regex_amd as R
+from regex_amd import Path
 from regex_amd import _native as N
 from oracle_py import OracleRegex
 
@@ -40,7 +41,7 @@ def test_big_batch_parity(cuda, force_big, pat, start):
     re = R.Regex(pat)
     o = OracleRegex(re)
     got_f = re.find_batch(d, stride=L, length=L, count=n, start=start).cpu().numpy()
-    assert N.rure_amd_last_fwd_path() == -6
+    assert N.last_path() == Path.BIG_DFA
     got_m = re.is_match_batch(d, stride=L, length=L, count=n, start=start).cpu().numpy()
     got_s = re.shortest_match_batch(d, stride=L, length=L, count=n, start=start).cpu().numpy()
     raw = buf.tobytes()
@@ -87,6 +88,6 @@ def test_big_default_threshold(cuda):
     buf = _hay(n, L, 77, b"abqxuz")
     d = torch.from_numpy(np.concatenate([buf, np.zeros(16, np.uint8)])).to(cuda)
     big = re.find_batch(d, stride=L, length=L, count=n).cpu().numpy()
-    assert N.rure_amd_last_fwd_path() == -6
+    assert N.last_path() == Path.BIG_DFA
     small = re.find_batch(d, stride=L, length=L, count=200).cpu().numpy()
     assert (small == big[:200]).all()

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import regex_amd as R
+from regex_amd import Path
 import regex_amd._native as N
 from golden_data import vectors
 from oracle_py import OracleRegex
@@ -71,7 +72,7 @@ def test_look_free(cuda, pat):
     texts = std_texts(pat)
     exp, _ = oracle_rows(pat, "std", texts)
     counts, groups, div = run_batch(re, texts, cuda, resolve=False)
-    assert N.rure_amd_last_fwd_path() == -28
+    assert N.last_path() == Path.CAPTURES_ITER
     assert div.shape == (len(texts),) and div.sum() == 0
     assert groups.shape[1:] == (re.captures_len(), 2)
     got = split_rows(counts, groups)
@@ -201,7 +202,7 @@ def test_replace_expand_batch(cuda, pat, rep):
     for limit in (0, 1, 3):
         out, ooff = re.replace_batch(dbuf, rep, limit=limit, offsets=doffs, expand=True)
         if b"$" in rep and pat != r"(a..$)|(a)":   # (resolving runs the single-haystack path last)
-            assert N.rure_amd_last_fwd_path() == -29
+            assert N.last_path() == Path.REPLACE_EXPAND
         out = out.cpu().numpy().tobytes()
         ooff = ooff.cpu().numpy()
         assert ooff[0] == 0 and ooff[-1] == len(out)
@@ -219,7 +220,7 @@ def test_expand_off_keeps_the_literal(cuda):
     for kw, rep in (({}, b"$1"), ({"expand": False}, b"$1"), ({"expand": True}, R.NoExpand(b"$1")),
                     ({"expand": True}, b"no dollar")):
         out, ooff = re.replace_batch(dbuf, rep, offsets=doffs, **kw)
-        assert N.rure_amd_last_fwd_path() != -29
+        assert N.last_path() != Path.REPLACE_EXPAND
         out, ooff = out.cpu().numpy().tobytes(), ooff.cpu().numpy()
         lit = rep.rep if isinstance(rep, R.NoExpand) else rep
         for i, t in enumerate(texts):
@@ -260,9 +261,9 @@ def test_strided_long(cuda):
     o = OracleRegex(re)
     dbuf = torch.from_numpy(buf).to(cuda)
     re.find_iter_batch(dbuf, stride=L, length=L, count=n)
-    assert N.rure_amd_last_fwd_path() in (-21, -25, -14, -15)   # chunked
+    assert N.last_path() in (Path.ITER_CHUNKED, Path.ITER_SHADOW_GATED, Path.ITER_SHADOW, Path.ITER_SHADOW_QUIT)   # chunked
     out, ooff = re.replace_batch(dbuf, b"$d/$m/$y", stride=L, length=L, count=n, expand=True)
-    assert N.rure_amd_last_fwd_path() == -29
+    assert N.last_path() == Path.REPLACE_EXPAND
     out = out.cpu().numpy().tobytes()
     ooff = ooff.cpu().numpy()
     assert ooff[-1] == len(out) == n * L   # dd/mm/yyyy is as long as yyyy-mm-dd

@@ -8,7 +8,7 @@ iteration must reproduce: units whose first reverse scan reaches their start
 (repaired from the true entry), reverse NoMatches that end the iteration
 (\\B at a unit start), and Unicode word boundaries whose DFA quits on
 non-ASCII bytes (the quitting units are served by the wave's Pike VM:
-last_fwd_path -27; tests/test_gpu_iter_wave.py).
+Path.ITER_WAVE_SERVED; tests/test_gpu_iter_wave.py).
 The debug knob iter_chunk forces small units (many boundaries)."""
 import os
 import random
@@ -18,11 +18,15 @@ import numpy as np
 import pytest
 
 import regex_amd as R
+from regex_amd import Path
 from regex_amd import _native as N
 from golden_data import corpus, stdlib_looks_fixtures
 from oracle_py import OracleRegex
 
 pytestmark = pytest.mark.gpu
+
+# a look-around regex answered by a chunked pass, none of them quitting
+CHUNKED_LOOKS = (Path.ITER_LOOKS, Path.ITER_SHADOW, Path.ITER_SHADOW_GATED, Path.ITER_WAVE_SERVED)
 
 ASCII_PATTERNS = [r"(?-u)\b[a-c]+\b", r"(?m)^a+", r"(?m)a+$", r"(?-u)\B[ab]+", r"(?m)^$", r"(?-u)\b",
                   r"(?-u)[a-d]*\bd", r"a+\z", r"(?-u)\B\w+", r"(?-u)\b|\B[ab]", r"(?m)^[^\n]*$",
@@ -48,7 +52,7 @@ def _dev(buf, cuda):
 def _run(re, buf, L, count, cuda, chunk, **kw):
     with R.debug(iter_chunk=chunk, **kw):
         counts, m = re.find_iter_batch(_dev(buf, cuda), stride=L, length=L, count=count)
-        return counts.cpu().numpy().tolist(), [tuple(x) for x in m.cpu().numpy().tolist()], N.rure_amd_last_fwd_path()
+        return counts.cpu().numpy().tolist(), [tuple(x) for x in m.cpu().numpy().tolist()], N.last_path()
 
 
 def _check(re, buf, L, count, cuda, chunk, **kw):
@@ -71,7 +75,7 @@ def test_find_iter_looks_chunked(cuda, pat, chunk):
     L = 6000
     for count, seed in ((1, 1), (3, 2)):
         buf = _text(zlib.crc32(pat.encode()) + seed, L * count, False)
-        assert _check(re, buf, L, count, cuda, chunk) in (-12, -14, -25, -27), pat
+        assert _check(re, buf, L, count, cuda, chunk) in CHUNKED_LOOKS, pat
 
 
 @pytest.mark.parametrize("pat", UNICODE_PATTERNS)
@@ -80,16 +84,16 @@ def test_find_iter_looks_chunked(cuda, pat, chunk):
 def test_find_iter_unicode_boundary(cuda, pat, nonascii, wave):
     """A DFA that can quit (Unicode \\b): ASCII text stays chunked; with
     non-ASCII bytes the units whose searches quit are served by the wave's
-    Pike VM inside the chunked iteration (-27); knob iter_wave=0 reads the
-    quit back and sends the batch to the wave path (-13)."""
+    Pike VM inside the chunked iteration (ITER_WAVE_SERVED); knob iter_wave=0 reads the
+    quit back and sends the batch to the wave path (ITER_LOOKS_QUIT)."""
     re = R.Regex(pat)
     L = 8000
     buf = _text(zlib.crc32(pat.encode()), L, nonascii)
     path = _check(re, buf, L, 1, cuda, 64, iter_wave=wave)
     if not nonascii:
-        assert path in (-12, -14, -25, -27), pat
+        assert path in CHUNKED_LOOKS, pat
     elif "\\b" in pat or "\\B" in pat:
-        assert path == (-27 if wave else -13), pat
+        assert path == (Path.ITER_WAVE_SERVED if wave else Path.ITER_LOOKS_QUIT), pat
 
 
 @pytest.mark.parametrize("pat", [r"\b\w+\b", r"(?m)^\w+", r"\bthe\b", r"(?-u:\b)[A-Z]\w*", r"\w+ing\b"])
@@ -101,7 +105,7 @@ def test_find_iter_looks_long_sherlock(cuda, pat):
     re = R.Regex(pat)
     import torch
     counts, m = re.find_iter_batch(_dev(text, cuda), stride=len(text), length=len(text), count=1)
-    assert N.rure_amd_last_fwd_path() in (-12, -14, -25, -27), pat
+    assert N.last_path() in CHUNKED_LOOKS, pat
     exp = OracleRegex(re).find_iter(text)
     assert [tuple(x) for x in m.cpu().numpy().tolist()] == exp
     del torch
@@ -117,7 +121,7 @@ def test_find_iter_looks_vs_stdlib(cuda, pat, chunk):
     for (off, n), exp in zip(fx["slices"], fx["find_iter"][pat]):
         counts, got, path = _run(re, text[off:off + n], n, 1, cuda, chunk)
         assert got == [tuple(x) for x in exp], (pat, off)
-        assert path in (-12, -14, -25, -27), pat
+        assert path in CHUNKED_LOOKS, pat
 
 
 @pytest.mark.parametrize("pat", [r"\w+", r"\w+\s+\w+", r"[\w.]+@\w+", r"\pL+", r"\w{2,4}", r"(?m)^\w+",
@@ -128,16 +132,17 @@ def test_find_iter_ascii_shadow(cuda, pat, nonascii, sync):
     """Unicode classes: the find_iter automaton's ASCII shadow (all-rows LDS
     tables, non-ASCII bytes quit) answers ASCII text; a non-ASCII byte makes
     the full automaton answer.  By default the quit stays on the device and
-    gates both passes, enqueued one after the other (last_fwd_path -25);
-    knob shadow_sync=1 reads it back (-14 the shadow answered, -15 the full
-    automaton re-ran)."""
+    gates both passes, enqueued one after the other (ITER_SHADOW_GATED);
+    knob shadow_sync=1 reads it back (ITER_SHADOW: the shadow answered,
+    ITER_SHADOW_QUIT: the full automaton re-ran)."""
     re = R.Regex(pat)
     L = 20000
     buf = _text(zlib.crc32(pat.encode()) + 5, L * 2, nonascii)
     path = _check(re, buf, L, 2, cuda, 64, shadow_sync=sync)
-    # (-19: the run engine of a C+ regex, which decodes UTF-8 and never quits)
+    # (ITER_RUNS: the run engine of a C+ regex, which decodes UTF-8 and never quits)
     if not sync:
-        assert path in (-25, -19), (pat, path)
+        assert path in (Path.ITER_SHADOW_GATED, Path.ITER_RUNS), (pat, path)
     else:
-        # (after a quit a look-around regex notes its own chunked path, -12)
-        assert path in ((-15, -12, -19) if nonascii else (-14, -19)), (pat, path)
+        # (after a quit a look-around regex notes its own chunked path, ITER_LOOKS)
+        assert path in ((Path.ITER_SHADOW_QUIT, Path.ITER_LOOKS, Path.ITER_RUNS) if nonascii
+                        else (Path.ITER_SHADOW, Path.ITER_RUNS)), (pat, path)

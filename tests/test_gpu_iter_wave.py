@@ -1,5 +1,5 @@
 r"""The wave-served chunked find_iter (iter_scan.hip iter_wspec_kernel ..
-iter_wemit_kernel, last_fwd_path -27) against the oracle's sequential
+iter_wemit_kernel, Path.ITER_WAVE_SERVED) against the oracle's sequential
 find_iter (re_trait.rs:197-221 over exec.rs:473-514), bit-exact.
 
 A Unicode \b makes the reference's lazy DFA quit on any byte >= 0x80
@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import regex_amd as R
+from regex_amd import Path
 from regex_amd import _native as N
 from golden_data import corpus, known_counts
 from oracle_py import OracleRegex
@@ -55,7 +56,7 @@ def _check(re, buf, L, count, cuda, chunk=None):
     kw = {"iter_chunk": chunk} if chunk else {}
     with R.debug(**kw):
         counts, m = re.find_iter_batch(_dev(buf, cuda), stride=L, length=L, count=count)
-        path = N.rure_amd_last_fwd_path()
+        path = N.last_path()
     got = [tuple(x) for x in m.cpu().numpy().tolist()]
     o = OracleRegex(re)
     k = 0
@@ -76,7 +77,7 @@ def test_wave_units_vs_oracle(cuda, pat, every, chunk):
     L = 24000 if chunk >= 509 else 6000
     for count, seed in ((1, 1), (3, 2)):
         buf = _text(zlib.crc32(pat.encode()) + seed * 7 + every, L * count, every)
-        assert _check(re, buf, L, count, cuda, chunk) == -27, pat
+        assert _check(re, buf, L, count, cuda, chunk) == Path.ITER_WAVE_SERVED, pat
 
 
 @pytest.mark.parametrize("pat", [r"\b\w+n\b", r"\b\w+\b"])
@@ -87,12 +88,12 @@ def test_wave_default_units(cuda, pat):
     t = corpus("sherlock")
     re = R.Regex(pat)
     t3 = (t * 4)[: 2 << 20]
-    assert _check(re, t3, len(t3), 1, cuda) == -27
+    assert _check(re, t3, len(t3), 1, cuda) == Path.ITER_WAVE_SERVED
     a = bytearray(t3)
     for i in range(0, len(a) - 1, 199):
         if 0x61 <= a[i] <= 0x7A and 0x61 <= a[i + 1] <= 0x7A:
             a[i], a[i + 1] = 0xC3, 0xA9
-    assert _check(re, bytes(a), len(a), 1, cuda) == -27
+    assert _check(re, bytes(a), len(a), 1, cuda) == Path.ITER_WAVE_SERVED
 
 
 def test_wave_empty_and_tiny(cuda):
@@ -119,7 +120,7 @@ def test_wave_sherlock_one_gib(cuda):
     big[:copies * len(t)].view(copies, len(t)).copy_(one.expand(copies, len(t)))
     n = copies * len(t)
     counts, m = re.find_iter_batch(big, stride=n, length=n, count=1, capacity=copies * e["count"] + copies * seam)
-    assert N.rure_amd_last_fwd_path() == -27
+    assert N.last_path() == Path.ITER_WAVE_SERVED
     assert int(counts[0]) == copies * e["count"] + (copies - 1) * seam
     exp = OracleRegex(re).find_iter(t)[:e["count"] - 1]
     got = [tuple(x) for x in m[:len(exp)].cpu().numpy().tolist()]

@@ -6,7 +6,7 @@ resumes them.  `(?:a|b)*a(?:a|b){20}` has ~2^21 states, past the eager
 budgets (kBigDfaRawStates), so it used to run on the Pike VM; debug knobs
 lazy=1, lazy_rows=1 (one row built ahead per round) force ordinary
 regexes through many parking rounds.  find / is_match / shortest_match
-against the oracle; rure_amd_last_fwd_path() == -10 asserts the lazy kernel
+against the oracle; last_path() == Path.LAZY_DFA asserts the lazy kernel
 answered."""
 import os
 
@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import regex_amd as R
+from regex_amd import Path
 from regex_amd import _native as N
 from oracle_py import OracleRegex
 from golden_data import corpus
@@ -44,7 +45,7 @@ def _check(cuda, pat, raw, n, L, start=0):
     o = OracleRegex(re)
     got_f = re.find_batch(d, stride=L, length=L, count=n, start=start).cpu().numpy()
     if re.match_info()["match_type"] == "Dfa":  # (literal / suffix match types run their own engines)
-        assert N.rure_amd_last_fwd_path() == -10, pat
+        assert N.last_path() == Path.LAZY_DFA, pat
     got_m = re.is_match_batch(d, stride=L, length=L, count=n, start=start).cpu().numpy()
     got_s = re.shortest_match_batch(d, stride=L, length=L, count=n, start=start).cpu().numpy()
     hits = 0
@@ -90,7 +91,7 @@ def test_lazy_offsets(cuda):
     d = torch.from_numpy(np.frombuffer(text + b"\0" * 16, dtype=np.uint8).copy()).to(cuda)
     with R.debug(big=2):
         got = re.find_batch(d, offsets=torch.from_numpy(offs).to(cuda)).cpu().numpy()
-        assert N.rure_amd_last_fwd_path() == -10
+        assert N.last_path() == Path.LAZY_DFA
     for i in range(len(offs) - 1):
         h = text[offs[i]:offs[i + 1]]
         e = o.find(h)

@@ -7,8 +7,8 @@ one-line-ahead prefetch meet: empty lines, 1-byte lines, lines inside one
 16-byte block, lines crossing many blocks, lines > 4 KiB, runs of empty lines
 at the end of the batch, lines carrying Unicode digits / word characters and
 invalid UTF-8 (the sentinel redo on the global table), and searches from
-start > 0 (look-behind from the byte before start).  rure_amd_last_fwd_path()
-== -8 asserts the line kernel ran; debug knob lines=0 gives the previous
+start > 0 (look-behind from the byte before start).  last_path()
+== Path.LINES asserts the line kernel ran; debug knob lines=0 gives the previous
 one-lane-per-haystack kernel, checked for the same answers.
 """
 import os
@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import regex_amd as R
+from regex_amd import Path
 from regex_amd import _native as N
 from oracle_py import OracleRegex
 from regex_amd.workloads import date_haystacks_host
@@ -55,7 +56,7 @@ def _check(cuda, re, o, buf, offs, start):
     d = torch.from_numpy(buf).to(cuda)
     od = torch.from_numpy(offs).to(cuda)
     got = re.find_batch(d, offsets=od, start=start).cpu().numpy()
-    path = N.rure_amd_last_fwd_path()
+    path = N.last_path()
     ism = re.is_match_batch(d, offsets=od, start=start).cpu().numpy()
     sho = re.shortest_match_batch(d, offsets=od, start=start).cpu().numpy()
     if start == 0:
@@ -102,7 +103,7 @@ def test_lines_path_taken(cuda):
     o = OracleRegex(re)
     buf, offs = _lines(5000, 7)
     path, _ = _check(cuda, re, o, buf, offs, 0)
-    assert path == -8
+    assert path == Path.LINES
 
 
 @pytest.mark.parametrize("pat", [r"\d{4}-\d{2}-\d{2}", r"\bfox\b", r"(?m)^\d+$"])

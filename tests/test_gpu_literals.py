@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import regex_amd as R
+from regex_amd import Path
 from golden_data import corpus, known_counts
 from oracle_py import OracleRegex
 from regex_amd.dist import find_iter_spans_local
@@ -195,7 +196,7 @@ def test_literal_find_batch_offsets(cuda, pat):
     buf, offs, dbuf, doffs = _offsets_batch(hs, cuda)
     for start in (0, 3):
         got = re.find_batch(dbuf, offsets=doffs, start=start).cpu().numpy().astype(np.uint64)
-        assert NN.rure_amd_last_fwd_path() == -3
+        assert NN.last_path() == Path.LITERAL
         exp = [o.find(h, start) if start <= len(h) else None for h in hs]
         for i, (h, e) in enumerate(zip(hs, exp)):
             g = None if got[i, 0] == np.uint64(2**64 - 1) else (int(got[i, 0]), int(got[i, 1]))
@@ -239,14 +240,14 @@ def test_literal_find_default_dispatch(cuda, knobs, nwords):
     buf = text[: n * L]
     d = dev(buf, cuda)
     got = re.find_batch(d, stride=L, length=L, count=n).cpu().numpy()
-    path = NN.rure_amd_last_fwd_path()
+    path = NN.last_path()
     gm = re.is_match_batch(d, stride=L, length=L, count=n).cpu().numpy()
-    assert (path == -3) == (nwords <= 8), path
-    assert NN.rure_amd_last_fwd_path() == path
+    assert (path == Path.LITERAL) == (nwords <= 8), path
+    assert NN.last_path() == path
     assert len(re.literals()) == nwords
     knobs(lit=0)
     ref = re.find_batch(d, stride=L, length=L, count=n).cpu().numpy()
-    assert NN.rure_amd_last_fwd_path() != -3
+    assert NN.last_path() != Path.LITERAL
     assert np.array_equal(got, ref)
     assert np.array_equal(gm, re.is_match_batch(d, stride=L, length=L, count=n).cpu().numpy())
     exp, _ = R_oracle_find(re, buf, L, n)

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import regex_amd as R
+from regex_amd import Path
 from regex_amd import _native as N
 from golden_data import corpus
 from oracle_py import OracleRegex
@@ -78,7 +79,7 @@ def test_batch_parity(cuda, pat, start):
     o = OracleRegex(re)
     got_f = re.find_batch(d, stride=L, length=L, count=n, start=start).cpu().numpy()
     if re.match_info()["match_type"] in ("DfaSuffix", "Literal(AnchoredStart)"):
-        assert N.rure_amd_last_fwd_path() == -5
+        assert N.last_path() == Path.LANE_SEARCH
     got_m = re.is_match_batch(d, stride=L, length=L, count=n, start=start).cpu().numpy()
     got_s = re.shortest_match_batch(d, stride=L, length=L, count=n, start=start).cpu().numpy()
     for i in range(n):

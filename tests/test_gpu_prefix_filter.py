@@ -1,6 +1,6 @@
 """GPU parity of the start-state prefix skip (FwdDfaDev::pfx_*; dfa.rs:700-711
 prefix_at restated as a burst filter) on the chunked long scan
-(last_fwd_path -4): find / is_match / shortest over long haystacks against
+(Path.LONG_SCAN): find / is_match / shortest over long haystacks against
 the oracle, with the only occurrence planted across 128-byte burst edges (a
 prefix whose first byte ends a burst must not be skipped) and case-folded
 prefix sets; without the skip (debug knob prefix=0), on the first byte
@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import regex_amd as R
+from regex_amd import Path
 from regex_amd import _native as N
 from oracle_py import OracleRegex
 
@@ -48,11 +49,11 @@ def test_prefix_filter_long_scan(cuda, pat, occ, where, prefix_mode):
     o = OracleRegex(re)
     d = torch.from_numpy(np.frombuffer(text + b"\0" * 16, dtype=np.uint8).copy()).to(cuda)
     f = re.find_batch(d, stride=L, length=L, count=1).cpu().numpy()
-    path = N.rure_amd_last_fwd_path()
+    path = N.last_path()
     m = re.is_match_batch(d, stride=L, length=L, count=1).cpu().numpy()
     exp = o.find(text)
     got = None if int(f[0, 0]) == -1 else (int(f[0, 0]), int(f[0, 1]))
     assert got == exp, (pat, where, got, exp)
     assert bool(m[0]) == (exp is not None)
     if re.match_info()["match_type"] == "Dfa":
-        assert path == -4, pat
+        assert path == Path.LONG_SCAN, pat

@@ -1,5 +1,5 @@
 """replace_all of a one-byte-class regex on the GPU without a match list
-(replace_scan.hip launch_replace_class, last_fwd_path -23) against the
+(replace_scan.hip launch_replace_class, Path.REPLACE_CLASS) against the
 oracle's find_iter + the reference's replacen rule (re_bytes.rs:489-512):
 sparse, dense and all-class text, replacements of 1 to 64 bytes, lengths
 around the 64-byte lane and 4 KiB unit edges, an output buffer smaller than
@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import regex_amd as R
+from regex_amd import Path
 from regex_amd import _native as N
 from oracle_py import OracleRegex
 
@@ -48,7 +49,7 @@ def test_replace_class(cuda, pat, alpha, n, rep):
     t = text(n * 7 + len(rep), n, alpha)
     out, ooff = re.replace_batch(dev(t, cuda), rep, stride=max(n, 1), length=n, count=1)
     if n:
-        assert N.rure_amd_last_fwd_path() == -23
+        assert N.last_path() == Path.REPLACE_CLASS
     assert bytes(out.cpu().numpy()) == expect(re, t, rep), (pat, n, rep)
     assert ooff.cpu().numpy().tolist() == [0, len(expect(re, t, rep))]
 
@@ -91,7 +92,7 @@ def test_iub_chain_known_length(cuda):
     for p, rep in shootout.SUBSTS:
         re = R.Regex(p.decode())
         out, ooff = re.replace_batch(cur, rep, stride=n, length=n, count=1)
-        assert N.rure_amd_last_fwd_path() == -23
+        assert N.last_path() == Path.REPLACE_CLASS
         n = int(ooff[1].item())
         import torch
         cur = torch.cat([out[:n], torch.zeros(16, dtype=torch.uint8, device=cuda)])
@@ -121,7 +122,7 @@ CHAINS = [
 def test_replace_chain(cuda, knobs, seq, ci, n):
     """rure_amd_replace_all_chain against the host rule applied step by step:
     the same bytes and every intermediate length — as one composed byte map
-    (default, last_fwd_path -24) and step by step (knob chain_seq=1, -23)."""
+    (default, REPLACE_HMAP) and step by step (knob chain_seq=1, REPLACE_CLASS)."""
     if seq:
         knobs(chain_seq=1)
     steps = [(R.Regex(p), rep) for p, rep in CHAINS[ci]]
@@ -136,7 +137,7 @@ def test_replace_chain(cuda, knobs, seq, ci, n):
     assert lengths.cpu().numpy().tolist() == lens
     assert bytes(out[:lens[-1]].cpu().numpy()) == exp
     if n:
-        assert N.rure_amd_last_fwd_path() == (-23 if seq else -24)
+        assert N.last_path() == (Path.REPLACE_CLASS if seq else Path.REPLACE_HMAP)
 
 
 @pytest.mark.parametrize("seq", [0, 1])
@@ -176,12 +177,12 @@ def test_replace_chain_rejects(cuda):
 
 def test_replace_chain_long_images(cuda):
     """Images longer than 64 bytes after composition (x -> 40 x, then each x
-    -> 2 x): the call runs the chain step by step (-23), same bytes."""
+    -> 2 x): the call runs the chain step by step (REPLACE_CLASS), same bytes."""
     steps = [(R.Regex(r"x"), b"x" * 40), (R.Regex(r"x"), b"xx")]
     t = text(9, 5000, b"xab")
     out, lengths = R.replace_all_chain([r for r, _ in steps], [rep for _, rep in steps], dev(t, cuda), length=len(t),
                                        capacity=100 * len(t))
-    assert N.rure_amd_last_fwd_path() == -23
+    assert N.last_path() == Path.REPLACE_CLASS
     exp = chain_expect(steps, t)
     assert int(lengths[-1]) == len(exp)
     assert bytes(out[:len(exp)].cpu().numpy()) == exp

@@ -1,4 +1,4 @@
-"""The find_iter run engine on the GPU (run_iter.hip, last_fwd_path -19):
+"""The find_iter run engine on the GPU (run_iter.hip, Path.ITER_RUNS):
 C+ regexes' matches = maximal runs, against the oracle's find_iter
 (re_trait.rs:197-221) — single long haystacks (runs crossing lanes and 4 KiB
 units, a run longer than many units, all-C text), fixed-stride batches,
@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import regex_amd as R
+from regex_amd import Path
 from regex_amd import _native as N
 from oracle_py import OracleRegex
 
@@ -39,7 +40,7 @@ def check_one(re, t, cuda, start=0, expect_path=None):
     assert int(counts[0]) == len(exp)
     assert got == exp
     if expect_path is not None:
-        assert N.rure_amd_last_fwd_path() == expect_path
+        assert N.last_path() == expect_path
 
 
 @pytest.mark.parametrize("pat", PATS)
@@ -47,7 +48,7 @@ def test_runs_sherlock(cuda, pat):
     t = sherlock()
     t = bytes(b if b < 0x80 else 0x20 for b in t)  # ASCII: the run engine answers
     re = R.Regex(pat)
-    check_one(re, t, cuda, expect_path=-19)
+    check_one(re, t, cuda, expect_path=Path.ITER_RUNS)
     check_one(re, t, cuda, start=4097)
 
 
@@ -62,7 +63,7 @@ def test_runs_long_and_all_c(cuda, pat):
         parts.append(b" " * rng.choice([1, 2, 64]))
     parts.append(b"b" * 100000)
     t = b"".join(parts)
-    check_one(re, t, cuda, expect_path=-19)
+    check_one(re, t, cuda, expect_path=Path.ITER_RUNS)
     check_one(re, b"z" * 70000, cuda)  # one run: the whole text
     check_one(re, b"z" * 8192, cuda)   # ... ending exactly at a unit edge
     check_one(re, b"", cuda)
@@ -94,17 +95,17 @@ def test_runs_non_ascii(cuda, pat):
     """Bytes >= 0x80: a Unicode class's engine decodes them as UTF-8 (valid
     letters, marks, digits, symbols, astral code points; stray
     continuations, truncated leads, overlong forms, surrogates, bytes past
-    U+10FFFF) and still answers (-19), with runs crossing lanes and units;
+    U+10FFFF) and still answers (ITER_RUNS), with runs crossing lanes and units;
     [a-z]+'s class is exact on every byte."""
     from test_run_engine import utf8_text
     re = R.Regex(pat)
     rng = random.Random(3)
     alpha = [b"ab", b"Z9", b" ", b"\n", "é".encode(), "✓".encode(), b"\xff", "٣".encode(), b"x_y"]
     t = b"".join(rng.choices(alpha, k=30000))
-    check_one(re, t, cuda, expect_path=-19)
+    check_one(re, t, cuda, expect_path=Path.ITER_RUNS)
     check_one(re, t, cuda, start=4097)
     u = utf8_text(zlib.crc32(pat.encode()), 40000)
-    check_one(re, u, cuda, expect_path=-19)
+    check_one(re, u, cuda, expect_path=Path.ITER_RUNS)
     for st in (1, 2, 63, 4095, 4097):
         check_one(re, u, cuda, start=st)
     # a multi-byte encoding straddling every lane and unit edge: é at 62-63,
@@ -114,7 +115,7 @@ def test_runs_non_ascii(cuda, pat):
     edge[4094:4097] = "中".encode()
     edge[8190:8194] = "\U0001d400".encode()
     edge[200:201] = b" "
-    check_one(re, bytes(edge), cuda, expect_path=-19)
+    check_one(re, bytes(edge), cuda, expect_path=Path.ITER_RUNS)
 
 
 def test_runs_sherlock_unicode(cuda):
@@ -123,6 +124,6 @@ def test_runs_sherlock_unicode(cuda):
     re = R.Regex(r"\w+")
     t = sherlock()
     assert any(b >= 0x80 for b in t)
-    check_one(re, t, cuda, expect_path=-19)
+    check_one(re, t, cuda, expect_path=Path.ITER_RUNS)
     counts, _ = re.find_iter_batch(dev(t, cuda), stride=len(t), length=len(t), count=1)
     assert int(counts[0]) == 109214

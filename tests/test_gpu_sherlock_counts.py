@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import regex_amd as R
+from regex_amd import Path
 from regex_amd import _native as N
 from golden_data import corpus, known_counts
 from oracle_py import OracleRegex
@@ -43,7 +44,7 @@ def test_words_one_gib(cuda):
     n = copies * len(t)
     counts, m = re.find_iter_batch(big, stride=n, length=n, count=1, capacity=1)
     assert int(counts[0]) == copies * words["count"] + (copies - 1) * seam
-    assert N.rure_amd_last_fwd_path() == -19, N.rure_amd_last_fwd_path()  # the run engine, Unicode \w
+    assert N.last_path() == Path.ITER_RUNS, N.last_path()  # the run engine, Unicode \w
     # the first copy's records equal the oracle's
     _, m = re.find_iter_batch(big, stride=n, length=n, count=1, capacity=words["count"])
     exp = OracleRegex(re).find_iter(t)[:words["count"] - 1]

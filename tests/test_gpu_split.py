@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import regex_amd as R
+from regex_amd import Path
 from regex_amd import _native as N
 from oracle_py import OracleRegex
 from unicode_mix import unicode_mix
@@ -43,7 +44,7 @@ def test_split_small_batch(cuda, knobs, pat, shape):
         got_s = re.shortest_match_batch(d, stride=S, length=L, count=n, start=start).cpu().numpy()
         got_m = re.is_match_batch(d, stride=S, length=L, count=n, start=start).cpu().numpy()
         if pat in SPLIT_PATS:  # only is_match takes the split (a find unit scans until the DFA dies)
-            assert N.rure_amd_last_fwd_path() == -4, (pat, shape)
+            assert N.last_path() == Path.LONG_SCAN, (pat, shape)
         knobs(split=0)
         ref_f = re.find_batch(d, stride=S, length=L, count=n, start=start).cpu().numpy()
         ref_m = re.is_match_batch(d, stride=S, length=L, count=n, start=start).cpu().numpy()

@@ -6,7 +6,7 @@ starts at an occurrence end, so each occurrence's slice is scanned once and
 the searches the iteration makes are found by pointer doubling.  Against the
 oracle's find_iter (the reference's search chain restated), including the
 walk's quirk (`xa*ingb*ing|a+ing`) and the None fallbacks ("singing":
-a reverse scan reaching its slice start).  rure_amd_last_fwd_path() == -11
+a reverse scan reaching its slice start).  last_path() == Path.SUFFIX_ITER
 asserts the path ran."""
 import os
 
@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import regex_amd as R
+from regex_amd import Path
 from regex_amd import _native as N
 from oracle_py import OracleRegex
 from golden_data import corpus
@@ -46,7 +47,7 @@ def _check(cuda, pat, count, L, seed, start=0, capacity=None):
     assert re.match_info()["match_type"] == "DfaSuffix", pat
     o = OracleRegex(re)
     counts, m = re.find_iter_batch(d, stride=L, length=L, count=count, start=start, capacity=capacity)
-    assert N.rure_amd_last_fwd_path() == -11, pat
+    assert N.last_path() == Path.SUFFIX_ITER, pat
     counts = counts.cpu().numpy().tolist()
     got = [tuple(x) for x in m.cpu().numpy().tolist()]
     exp_all = []
@@ -94,7 +95,7 @@ def test_suffix_iter_quit_falls_back(cuda):
         got = [tuple(x) for x in m.cpu().numpy().tolist()]
         assert got == o.find_iter(t), pat
         if t == text:
-            assert N.rure_amd_last_fwd_path() == -11, pat
+            assert N.last_path() == Path.SUFFIX_ITER, pat
 
 
 def test_suffix_iter_capacity_and_empty(cuda):

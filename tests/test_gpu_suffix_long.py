@@ -6,7 +6,7 @@ forward DFA (None: a reverse scan reached its slice start, e.g. "singing")
 on the chunked forward scan.  find / is_match / shortest_match against the
 oracle, which restates the reference's sequential walk; patterns whose
 longest common suffix overlaps itself keep one lane per haystack.
-rure_amd_last_fwd_path() == -9 asserts the unit path ran (for the forward
+last_path() == Path.SUFFIX_LONG asserts the unit path ran (for the forward
 fallback the long scan's path code follows it)."""
 import os
 
@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import regex_amd as R
+from regex_amd import Path
 from regex_amd import _native as N
 from oracle_py import OracleRegex
 from golden_data import corpus
@@ -46,7 +47,7 @@ def _check(cuda, pat, count, L, seed, expect_path=None):
     assert re.match_info()["match_type"] == "DfaSuffix"
     o = OracleRegex(re)
     got = re.find_batch(d, stride=L, length=L, count=count).cpu().numpy()
-    path = N.rure_amd_last_fwd_path()
+    path = N.last_path()
     ism = re.is_match_batch(d, stride=L, length=L, count=count).cpu().numpy()
     sho = re.shortest_match_batch(d, stride=L, length=L, count=count).cpu().numpy()
     for h in range(count):
@@ -64,7 +65,7 @@ def _check(cuda, pat, count, L, seed, expect_path=None):
 
 @pytest.mark.parametrize("pat", [r"[a-z]+ing", r"\w+@gmail\.com"])
 def test_suffix_long(cuda, pat):
-    _check(cuda, pat, 3, 700_000, 11, expect_path=(-9, -4))  # -4: the forward fallback ran last
+    _check(cuda, pat, 3, 700_000, 11, expect_path=(Path.SUFFIX_LONG, Path.LONG_SCAN))  # LONG_SCAN: the forward fallback ran last
     _check(cuda, pat, 1, 4_000_000, 12)
 
 
@@ -95,7 +96,7 @@ def test_suffix_long_no_occurrence(cuda):
 def test_suffix_bordered_keeps_lanes(cuda, pat):
     """a self-overlapping lcs ("ingi", "abab"): the greedy occurrence walk is
     not every occurrence, so the lane search answers"""
-    _check(cuda, pat, 2, 300_000, 21, expect_path=(-5,))
+    _check(cuda, pat, 2, 300_000, 21, expect_path=(Path.LANE_SEARCH,))
 
 
 def test_suffix_walk_differs_from_forward(cuda):
@@ -118,4 +119,4 @@ def test_suffix_walk_differs_from_forward(cuda):
     d = torch.from_numpy(np.frombuffer(text + b"\0" * 16, dtype=np.uint8).copy()).to(cuda)
     got = re.find_batch(d, stride=L, length=L, count=1).cpu().numpy()[0].tolist()
     assert got == list(o.find(text)) == [L - 99, L - 94]
-    assert N.rure_amd_last_fwd_path() == -9
+    assert N.last_path() == Path.SUFFIX_LONG

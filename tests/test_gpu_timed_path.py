@@ -8,12 +8,13 @@ table when the DFA has one.  Both are compared here with the oracle (the
 restated lazy DFA, dfa.rs:576-764 / exec.rs:632-662), on the printable-ASCII
 date recipe and on haystacks carrying Unicode digits, multi-byte word
 characters and invalid UTF-8 (the sentinel redo on the global u16 table).
-rure_amd_last_fwd_path() asserts which kernel ran.
+last_path() asserts which kernel ran.
 """
 import numpy as np
 import pytest
 
 import regex_amd as R
+from regex_amd import Path
 from regex_amd import _native as N
 from oracle_py import OracleRegex
 from regex_amd.workloads import date_haystacks_host
@@ -39,7 +40,7 @@ def _check(cuda, pat, n, L, seed, mix, expect_path):
     o = OracleRegex(re)
     dev = torch.from_numpy(buf).to(cuda)
     got = re.find_batch(dev, stride=L, length=L, count=n).cpu().numpy()
-    path = N.rure_amd_last_fwd_path()
+    path = N.last_path()
     exp, _ = o.find_batch(buf, L, L, n, nthreads=8)
     exp = exp.astype(np.int64)
     bad = np.nonzero((got != exp).any(axis=1))[0]
@@ -47,7 +48,7 @@ def _check(cuda, pat, n, L, seed, mix, expect_path):
     if expect_path is not None:
         assert path in expect_path, (pat, n, path)
     ism = re.is_match_batch(dev, stride=L, length=L, count=n).cpu().numpy()
-    assert N.rure_amd_last_fwd_path() == path
+    assert N.last_path() == path
     iexp = o.is_match_batch(buf, L, L, n, nthreads=8)
     assert np.array_equal(ism.astype(bool), iexp.astype(bool))
     sho = re.shortest_match_batch(dev, stride=L, length=L, count=n).cpu().numpy()
@@ -62,7 +63,7 @@ def _check(cuda, pat, n, L, seed, mix, expect_path):
 def test_date_byte_table_above_threshold(cuda, mix):
     """140,000 x 128 B fixed-stride haystacks: above the 131,072 threshold, so
     the STRIDE = 1 tile kernel (the C2 timed instantiation) runs."""
-    got = _check(cuda, DATE, 140_000, 128, 0x7171, mix, expect_path=(1,))
+    got = _check(cuda, DATE, 140_000, 128, 0x7171, mix, expect_path=(Path.TILE1,))
     assert (got[:, 0] >= 0).sum() > 5000
 
 
@@ -76,12 +77,12 @@ def test_date_multibyte_table_below_threshold(cuda, mix):
 
 @pytest.mark.parametrize("n", [20_000, 140_000])
 def test_email_tile_unicode(cuda, n):
-    _check(cuda, EMAIL, n, 128, 0x7373 + n, True, expect_path=(1, 2, 4))
+    _check(cuda, EMAIL, n, 128, 0x7373 + n, True, expect_path=(Path.TILE1, Path.TILE2, Path.TILE4))
 
 
 def test_date_tile_long_unicode(cuda):
     """4 KiB haystacks (the C2 shape) with Unicode tokens, above the threshold."""
-    _check(cuda, DATE, 132_000, 1024, 0x7474, True, expect_path=(1,))
+    _check(cuda, DATE, 132_000, 1024, 0x7474, True, expect_path=(Path.TILE1,))
 
 
 def test_ragged_unicode(cuda):
@@ -99,6 +100,6 @@ def test_ragged_unicode(cuda):
         re = R.Regex(pat)
         o = OracleRegex(re)
         got = re.find_batch(torch.from_numpy(buf).to(cuda), offsets=torch.from_numpy(offs).to(cuda)).cpu().numpy()
-        assert N.rure_amd_last_fwd_path() == -8  # dfa_line_kernel
+        assert N.last_path() == Path.LINES  # dfa_line_kernel
         exp, _ = o.find_batch(buf, 0, 0, n, nthreads=8, offsets=offs.astype(np.uint64))
         assert np.array_equal(got, exp.astype(np.int64)), pat

@@ -3,9 +3,9 @@ r"""Unicode classes against Python's `re`, not against the product's front end
 points whose \w / \d / \s / L / case-fold membership agrees with the
 reference's Unicode 10 tables).  The oracle runs the product's compiled
 programs, so these fixtures are what catches a class the parser or the
-tables got wrong on both sides.  Paths: the run engine (-19) for the C+
+tables got wrong on both sides.  Paths: the run engine (ITER_RUNS) for the C+
 regexes, the per-line and per-lane kernels for ragged batches, the C2 tile
-kernel (path 1, above 131,072 fixed-stride haystacks) and the chunked long
+kernel (TILE1, above 131,072 fixed-stride haystacks) and the chunked long
 scan for C5's regex."""
 import gzip
 import json
@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import regex_amd as R
+from regex_amd import Path
 from regex_amd import _native as N
 
 pytestmark = pytest.mark.gpu
@@ -82,7 +83,7 @@ def test_unicode_long_find_iter(cuda, pat):
         d = torch.from_numpy(np.frombuffer(b + bytes(16), dtype=np.uint8).copy()).to(cuda)
         counts, m = re.find_iter_batch(d, stride=len(b), length=len(b), count=1)
         if pat in RUNS:
-            assert N.rure_amd_last_fwd_path() == -19, pat
+            assert N.last_path() == Path.ITER_RUNS, pat
         assert int(counts[0]) == len(flat) // 2
         assert [tuple(x) for x in m.cpu().numpy().tolist()] == pairs(flat)
 
@@ -100,7 +101,7 @@ def test_unicode_stride_tile(cuda, pat):
     re = R.Regex(pat)
     got = re.find_batch(d, stride=L, length=L, count=n).cpu().numpy()
     if pat in (r"\d{4}-\d{2}-\d{2}", r"\w+@\w+\.\w+"):
-        assert N.rure_amd_last_fwd_path() in (1, 2, 4), pat
+        assert N.last_path() in (Path.TILE1, Path.TILE2, Path.TILE4), pat
     exp = np.array([x[:2] if x else [-1, -1] for x in FX["spans"][pat]["stride"]] * rep, dtype=np.int64)
     bad = np.nonzero((got != exp).any(axis=1))[0]
     assert bad.size == 0, (int(bad[0]), got[bad[0]].tolist(), exp[bad[0]].tolist())

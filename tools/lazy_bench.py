@@ -3,7 +3,7 @@ regex past the eager budgets, `(?:a|b)*a(?:a|b){20}`, over a batch of
 sherlock lines mixed with a/b runs: first call (the eager attempt that
 fails, then the rounds that build the rows the text needs) and steady state
 (every row the text visits built: one round), against the Pike VM
-(lazy=0; its path is -16, the Pike VM alone).  Prints one JSON line per mode.
+(lazy=0; its path is Path.PIKE_ONLY, the Pike VM alone).  Prints one JSON line per mode.
 usage: python tools/lazy_bench.py [haystacks] [length] [sparse|dense]"""
 import json
 import os

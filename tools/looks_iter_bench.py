@@ -1,6 +1,6 @@
 """find_iter of look-around regexes over 1 GiB of sherlock text (made ASCII,
 so Unicode \\b's DFA never quits): the chunked path (iter_scan.hip with
-FwdDfaDev::looks, last_fwd_path -12) against the wave path
+FwdDfaDev::looks, Path.ITER_LOOKS) against the wave path
 (knob iter_looks=0) on a 16 MiB prefix, outputs compared there.
 --ragged: the same text as a ragged batch of its lines (one unit per line)
 against the wave path, outputs compared.

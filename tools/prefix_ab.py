@@ -1,5 +1,5 @@
 """A/B of the start-state prefix skip (dfa.rs:700-711) on the chunked long
-scan (long_scan_kernel, last_fwd_path -4) over ~1 GiB of sherlock text as one
+scan (long_scan_kernel, Path.LONG_SCAN) over ~1 GiB of sherlock text as one
 haystack: no skip (debug knob prefix=0), the first-byte skip (prefix=1,
 FwdDfaDev::pfx_*), the rarest byte or byte pair skip (prefix=2,
 FwdDfaDev::rare_*: the reference's FreqyPacked choice, literals.rs:390-510,

@@ -1,5 +1,5 @@
-"""find_iter of C+ regexes (the run engine, run_iter.hip, last_fwd_path
--19) over 1 GiB of sherlock text (as it is, with its non-ASCII bytes; or
+"""find_iter of C+ regexes (the run engine, run_iter.hip,
+Path.ITER_RUNS) over 1 GiB of sherlock text (as it is, with its non-ASCII bytes; or
 made ASCII with --ascii), against the DFA paths (knob runs=0: the ASCII
 shadow / chunked iteration); outputs of the two compared in full (count and
 every record).  One JSON line per pattern.

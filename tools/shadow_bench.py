@@ -1,7 +1,7 @@
 """find_iter of regexes that take the ASCII shadow automaton (DESIGN §4.3:
-by default the shadow's quit is a device flag gating both passes, path -25;
-with knob shadow_sync=1 it is read back, -14 = the shadow answered, -15 = a
-unit quit on a non-ASCII byte and the batch re-ran on the full automaton)
+by default the shadow's quit is a device flag gating both passes, Path.ITER_SHADOW_GATED;
+with knob shadow_sync=1 it is read back, ITER_SHADOW = the shadow answered,
+ITER_SHADOW_QUIT = a unit quit on a non-ASCII byte and the batch re-ran on the full automaton)
 against the full automaton alone (knob ascii_shadow=0), over 1 GiB of sherlock text three ways: made
 ASCII, as it is (sparse non-ASCII bytes), and dense (every 64th byte's word
 turned into a two-byte UTF-8 letter).  Outputs of the two compared in full.

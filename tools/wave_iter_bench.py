@@ -1,4 +1,4 @@
-"""The wave-served chunked find_iter (last_fwd_path -27) over 1 GiB of
+"""The wave-served chunked find_iter (Path.ITER_WAVE_SERVED) over 1 GiB of
 sherlock: as it is (33 non-ASCII bytes per 594 KB copy quit the DFA of a
 Unicode \\b) and made ASCII; on ASCII text also with knob iter_wave=0 (the
 plain chunked iteration that reads its quit flag back, -12), the cost of
