@@ -154,8 +154,12 @@ int rure_amd_set_matches_batch_words(rure_set *re, const rure_amd_batch *batch, 
  * counts[i] (device) = number of matches in haystack i; `matches` (device)
  * receives them concatenated in haystack order, at most `capacity` records;
  * *total (device) = the number of matches (rerun with a larger buffer if it
- * exceeds `capacity`).  Long fixed-stride haystacks are scanned in parallel
- * chunks with exact boundary repair. */
+ * exceeds `capacity`).  Long haystacks are scanned in parallel chunks with
+ * exact boundary repair: fixed-stride batches by their length, and offset
+ * batches (documents of their own lengths) when a haystack has 256 KiB or
+ * more to search, each haystack then cut by its own length.  An offset batch
+ * synchronises the stream once to read the longest and the total length back
+ * (16 bytes), and once more when it is chunked (the number of chunks). */
 int rure_amd_find_iter_batch(rure *re, const rure_amd_batch *batch, uint64_t *counts, rure_match *matches,
                              size_t capacity, uint64_t *total, void *stream);
 
@@ -490,6 +494,12 @@ int rure_amd_match_info_get(rure *re, rure_amd_match_info *info);
 /* 1 if batched searches of this regex run the DFA kernels, 0 if only the
  * Pike VM kernel (automaton too large), negative on error. */
 int rure_amd_uses_dfa(rure *re);
+/* 1 if the regex is of the DfaSuffix match type and no match of it holds its
+ * longest common suffix anywhere but at its end, so that its find_iter is
+ * the forward DFA's (host only; an offset batch with a long haystack then
+ * takes the chunked find_iter instead of one wavefront per haystack); 0 if
+ * not, negative on error. */
+int rure_amd_suffix_forward(rure *re);
 int rure_amd_set_uses_dfa(rure_set *re);
 /* Diagnostics (host only): the engine that answered a batched call.  The
  * values are frozen (recorded profiles hold them); a new engine takes a new
@@ -529,6 +539,12 @@ typedef enum rure_amd_path {
 /* The rure_amd_path of the last batched launch of this process (one value
  * for the whole process, not per thread or stream). */
 int rure_amd_last_fwd_path(void);
+/* Diagnostics (host only, one value for the whole process likewise): the
+ * number of units (chunks) the last chunked find_iter launch cut its batch
+ * into; *haystacks (may be NULL) = that batch's haystack count.  One unit per
+ * haystack means nothing was cut.  0 and *haystacks = 0 before the first such
+ * launch. */
+uint64_t rure_amd_last_iter_units(uint64_t *haystacks);
 /* Debug-only overrides of the engine dispatch and launch geometry
  * (regex_amd/csrc/host/knobs.hpp lists them): replaces the whole override
  * table, read once per process from RURE_AMD_DEBUG, by spec

@@ -159,8 +159,10 @@ rure_amd_find_iter_span_multi = _sig("rure_amd_find_iter_span_multi", ctypes.c_i
 rure_amd_literals_export = _sig("rure_amd_literals_export", ctypes.c_int64, VP, VP, VP, c_size)
 rure_amd_shiftand_export = _sig("rure_amd_shiftand_export", ctypes.c_int64, VP, VP, VP, VP, VP)
 rure_amd_uses_dfa = _sig("rure_amd_uses_dfa", ctypes.c_int, VP)
+rure_amd_suffix_forward = _sig("rure_amd_suffix_forward", ctypes.c_int, VP)
 rure_amd_set_uses_dfa = _sig("rure_amd_set_uses_dfa", ctypes.c_int, VP)
 rure_amd_last_fwd_path = _sig("rure_amd_last_fwd_path", ctypes.c_int)
+rure_amd_last_iter_units = _sig("rure_amd_last_iter_units", ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64))
 
 
 class Path(enum.IntEnum):
@@ -200,6 +202,14 @@ class Path(enum.IntEnum):
 def last_path():
     """The engine that answered the last batched launch of this process."""
     return Path(rure_amd_last_fwd_path())
+
+
+def last_iter_units():
+    """(units, haystacks) of the last chunked find_iter launch of this process:
+    units == haystacks means no haystack was cut; (0, 0) before the first."""
+    n = ctypes.c_uint64(0)
+    units = rure_amd_last_iter_units(ctypes.byref(n))
+    return int(units), int(n.value)
 
 
 rure_amd_debug_set = _sig("rure_amd_debug_set", ctypes.c_int, ctypes.c_char_p)

@@ -1266,6 +1266,72 @@ bool build_lex4(const std::vector<uint8_t> &img, uint32_t s0, std::vector<uint8_
   return true;
 }
 
+// Whether a DfaSuffix regex's find_iter is the forward DFA's (rure::
+// suffix_fwd): true when no leftmost-first match holds the longest common
+// suffix anywhere but at its end.  The reference's suffix walk (exec.rs:725-
+// 794) visits the lcs occurrences from the search start p in order; at each,
+// the reverse DFA over text[p..end] gives the leftmost s' with text[s'..end]
+// a match, and the forward DFA from s' the end; where it gives up, the
+// forward DFA answers.  Let m = (s, e) be the forward DFA's match from p: s
+// is the leftmost start of any match, and m ends with the occurrence O.  A
+// decided occurrence O' before O has s' >= s and its end inside m, so m would
+// hold O' inside: excluded.  At O the reverse scan finds s (nothing starts
+// further left) and the forward DFA from s ends at e.  (`xa*ingb*ing|a+ing`
+// over `xaaingbing` is the counter-example: its match (0, 10) holds an
+// earlier `ing`.)  Checked on the product of the anchored find_iter automaton
+// (strip[start]; a start that does not depend on look-behind, no quit state)
+// and the lcs's KMP automaton: no path that completes the lcs and reads at
+// least one more byte may end where a match is reported (the next state's
+// one-byte-delayed flag, or the EOF flag).  Conservative: false also where
+// the product is large.  The caller adds: no look-around, an lcs that cannot
+// overlap itself (every occurrence is walked).
+static bool suffix_only_at_end(const DenseDfa &d, uint32_t ustart1, const std::string &lcs) {
+  const size_t L = lcs.size();
+  if (!ustart1 || d.strip.empty() || d.trans.empty() || d.quit >= 0 || L == 0) return false;
+  if ((size_t)d.nstates * (L + 1) > (1u << 18)) return false;
+  // KMP automaton: k = the longest prefix of lcs that is a suffix of the text read
+  std::vector<uint32_t> fail(L + 1, 0), kmp((L + 1) * 256, 0);
+  for (size_t i = 1, k = 0; i < L; ++i) {
+    while (k && lcs[i] != lcs[k]) k = fail[k];
+    if (lcs[i] == lcs[k]) ++k;
+    fail[i + 1] = (uint32_t)k;
+  }
+  for (size_t k = 0; k <= L; ++k)
+    for (int c = 0; c < 256; ++c) {
+      if (k < L && (uint8_t)lcs[k] == c) kmp[k * 256 + c] = (uint32_t)k + 1;
+      else kmp[k * 256 + c] = k ? kmp[fail[k] * 256 + c] : 0;
+    }
+  auto flagged = [&](uint32_t t) { return (int)t >= d.n_normal && (int)t < d.n_match_end; };
+  // whether the text read up to state x is reported as a match
+  std::vector<uint8_t> reports(d.nstates, 0);
+  for (int x = 0; x < d.nstates; ++x) {
+    if ((size_t)x < d.eof_match.size() && d.eof_match[x]) reports[x] = 1;
+    for (int c = 0; c < 256 && !reports[x]; ++c) reports[x] = flagged(d.trans[(size_t)x * 256 + c]);
+  }
+  // product states (x, k, g): g = the lcs was complete before the last byte read
+  const uint32_t a0 = d.strip[ustart1 - 1];
+  std::vector<uint8_t> seen((size_t)d.nstates * (L + 1) * 2, 0);
+  auto idx = [&](uint32_t x, uint32_t k, uint32_t g) { return ((size_t)x * (L + 1) + k) * 2 + g; };
+  struct P { uint32_t x, k, g; };
+  std::vector<P> todo{{a0, 0, 0}};
+  seen[idx(a0, 0, 0)] = 1;
+  while (!todo.empty()) {
+    const P p = todo.back();
+    todo.pop_back();
+    for (int c = 0; c < 256; ++c) {
+      const uint32_t t = d.trans[(size_t)p.x * 256 + c];
+      if ((int)t == d.dead) continue;
+      const uint32_t g2 = p.g | (p.k == L ? 1u : 0u), k2 = kmp[(size_t)p.k * 256 + c];
+      if (g2 && reports[t]) return false;
+      if (!seen[idx(t, k2, g2)]) {
+        seen[idx(t, k2, g2)] = 1;
+        todo.push_back({t, k2, g2});
+      }
+    }
+  }
+  return true;
+}
+
 bool build_iter_dfa(rure *re) {
   if (!build_regex_dfas(re)) return false;
   std::lock_guard<std::mutex> g(re->mu);
@@ -1277,6 +1343,8 @@ bool build_iter_dfa(rure *re) {
     re->iter_ok = build_dense_dfa(re->fwd, lim, &re->dfwd_iter, &e) && pack_forward(re->dfwd_iter, &re->pf_iter, &e, true);
     if (!re->lits_done) re->lit_ok = extract_literals(re->nfa, kLitMax, kLitLen, &re->lits);
     re->lits_done = true;
+    re->suffix_fwd = re->iter_ok && re->xl.match_type == MT_DFA_SUFFIX && !re->nt.looks_used &&
+                     suffix_only_at_end(re->dfwd_iter, re->pf_iter.ustart1, re->xl.suffixes.lcs);
     bool fb_holds = false;
     if (re->iter_ok)
       re->fb_n = first_byte_rule(re->dfwd_iter, re->pf_iter.ustart1, !can_match_empty(re->nfa), re->fb_bytes,

@@ -1180,6 +1180,11 @@ int rure_amd_uses_dfa(rure *re) {
 }
 
 int rure_amd_last_fwd_path(void) { return rure_amd::last_fwd_path(); }
+uint64_t rure_amd_last_iter_units(uint64_t *haystacks) { return rure_amd::last_iter_units(haystacks); }
+int rure_amd_suffix_forward(rure *re) {
+  if (!re) return RURE_AMD_ERR_ARG;
+  return build_iter_dfa(re) && re->suffix_fwd ? 1 : 0;
+}
 int rure_amd_debug_set(const char *spec) { return rure_amd::knob_set(spec) ? RURE_AMD_OK : RURE_AMD_ERR_ARG; }
 
 

@@ -11,6 +11,20 @@ static std::atomic<int> g_last_fwd_path{RURE_AMD_PATH_NONE};
 int last_fwd_path() { return g_last_fwd_path.load(); }
 void note_fwd_path(rure_amd_path path) { g_last_fwd_path.store(path); }
 
+// rure_amd_last_iter_units: likewise (the pair under one lock).
+static std::mutex g_iter_units_mu;
+static uint64_t g_iter_units[2] = {0, 0};
+uint64_t last_iter_units(uint64_t *haystacks) {
+  std::lock_guard<std::mutex> g(g_iter_units_mu);
+  if (haystacks) *haystacks = g_iter_units[1];
+  return g_iter_units[0];
+}
+void note_iter_units(uint64_t units, uint64_t haystacks) {
+  std::lock_guard<std::mutex> g(g_iter_units_mu);
+  g_iter_units[0] = units;
+  g_iter_units[1] = haystacks;
+}
+
 }  // namespace rure_amd
 
 namespace rt {
@@ -525,6 +539,57 @@ int set_batch_group(rure_set *g, const rure_amd_batch *batch, const BatchDev &b,
 
 
 
+// Scratch released (stream-ordered) when the scope ends, whichever return is taken.
+struct ScratchHold {
+  void *p = nullptr;
+  hipStream_t st = nullptr;
+  ~ScratchHold() { (void)scratch_free(p, st); }
+};
+
+// The unit geometry of an offset batch (documents of their own lengths) in
+// the chunked find_iter.  One unit per haystack (rag->uoff stays null) unless
+// a haystack is long: one 64 MiB document among short ones would be iterated
+// by a single lane.  The longest and the total span are reduced on the
+// device and read back (16 bytes, one synchronisation); from 256 KiB (the
+// threshold of long_batch and the suffix iteration) the batch is cut into
+// units of about total / lanes-in-flight bytes, a haystack shorter than that
+// keeping its one unit (iter_device.hpp Geo::uoff), and the unit total is read
+// back (a second synchronisation, this path only) so that the scratch is
+// sized by the units there are.  Knob iter_ragged: 0 never, 2 at any length
+// (tests, with iter_chunk: many boundaries).
+static hipError_t ragged_plan(const BatchDev &b, int cus, hipStream_t st, uint64_t *chunk, IterRagged *rag,
+                              ScratchHold *hold) {
+  rag->uoff = nullptr;
+  const long long mode = knob(Knob::IterRagged);
+  if (mode == 0) return hipSuccess;
+  hipError_t e;
+  uint64_t span[2] = {0, 0};  // longest, total
+  {
+    ScratchHold stats{nullptr, st};
+    if ((e = scratch_malloc(&stats.p, 16, st)) != hipSuccess) return e;
+    if ((e = launch_iter_span_stats(b, (uint64_t *)stats.p, st, cus)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(span, stats.p, 16, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
+  }
+  if (mode != 2 && span[0] < (256u << 10)) return hipSuccess;
+  // the fixed-stride rule's lanes in flight, over the batch's bytes
+  uint64_t per_cu = 1024;
+  if (knob(Knob::IterLanes) > 0) per_cu = std::max<uint64_t>(64, knob(Knob::IterLanes));
+  uint64_t c = odd_lines(std::max<uint64_t>(4096, span[1] / ((uint64_t)cus * per_cu)));
+  if (knob(Knob::IterChunk) > 0) c = std::max<uint64_t>(16, knob(Knob::IterChunk));
+  const size_t n = b.count + 1;
+  hold->st = st;
+  if ((e = scratch_malloc(&hold->p, 2 * n * 8, st)) != hipSuccess) return e;
+  uint64_t *nk = (uint64_t *)hold->p, *uoff = nk + n;
+  if ((e = launch_iter_ragged_units(b, c, nk, uoff, st)) != hipSuccess) return e;
+  uint64_t nunits = 0;
+  if ((e = hipMemcpyAsync(&nunits, uoff + b.count, 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+  if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
+  *chunk = c;
+  *rag = IterRagged{uoff, nunits, span[1]};
+  return hipSuccess;
+}
+
 // The batched find_iter (re_trait.rs:197-221) on one stream.
 hipError_t run_find_iter(rure *re, DevTables *t, const BatchDev &b, const IterOut &o, hipStream_t st,
                          std::string *err, const IterSpan *sp) {
@@ -562,7 +627,14 @@ hipError_t run_find_iter(rure *re, DevTables *t, const BatchDev &b, const IterOu
   // The reference's Literal / DfaSuffix searches (DevTables::mt_lane): every
   // search of the iteration is one of those, on a wave per haystack (lane 0
   // searches, the wave runs the Pike VM where a DfaSuffix scan quits).
-  if (lane_search_ok(*t) && re->nfa_ok)
+  // Except an offset batch of a DfaSuffix regex whose iteration is the
+  // forward DFA's (rure::suffix_fwd; an lcs that cannot overlap itself, no
+  // quit): it takes the chunked iteration below, where a long haystack is cut
+  // into units (one wave would walk a 64 MiB document alone: 10 s) and a
+  // short one is a lane's, not a wave's.
+  const bool suffix_fwd = t->m.mt == MT_DFA_SUFFIX && t->lcs_free && !t->quit_possible && b.offs && !sp && b.count &&
+                          build_iter_dfa(re) && re->suffix_fwd;
+  if (lane_search_ok(*t) && re->nfa_ok && !suffix_fwd)
     return launch_find_iter_wave(b, t->has_dfa ? &t->f : nullptr, t->r, t->n, o, st, t->cus, sp, &t->m);
   // Chunked speculative iteration (iter_scan.hip); otherwise one wave per
   // haystack.  With look-around (or a DFA that can quit) it needs the
@@ -590,6 +662,14 @@ hipError_t run_find_iter(rure *re, DevTables *t, const BatchDev &b, const IterOu
       // knob iter_chunk: the unit size in bytes (tests: many boundaries)
       if (knob(Knob::IterChunk) > 0) chunk = std::max<uint64_t>(16, knob(Knob::IterChunk));
     }
+    // offset batches: the ragged geometry when a haystack is long (ragged_plan)
+    IterRagged ragged{};
+    ScratchHold ragged_buf;
+    if (b.offs && !sp && b.count) {
+      const hipError_t e = ragged_plan(b, t->cus, st, &chunk, &ragged, &ragged_buf);
+      if (e != hipSuccess) return e;
+    }
+    const IterRagged *const rag = ragged.uoff ? &ragged : nullptr;
     // A regex that is one class repeated (C+: [a-z]+, (?-u)\w+, and Unicode
     // classes \w+, \S+, \pL+ over UTF-8): its matches are the maximal runs
     // (run_iter.hip), no DFA walk; the ASCII shadow's class (an ASCII-only
@@ -631,12 +711,12 @@ hipError_t run_find_iter(rure *re, DevTables *t, const BatchDev &b, const IterOu
           hipError_t e = scratch_malloc((void **)&qf, 8, st);
           if (e == hipSuccess) e = hipMemsetAsync(qf, 0, 4, st);
           if (e == hipSuccess)
-            e = launch_find_iter_chunked(b, *fa, t->r, chunk, o, st, t->cus, IterQuit::device_word(qf));
+            e = launch_find_iter_chunked(b, *fa, t->r, chunk, o, st, t->cus, IterQuit::device_word(qf), nullptr, rag);
           if (e == hipSuccess) {
             BatchDev bf = b;
             bf.gate = qf;
             bf.gate_set = 1;
-            e = launch_find_iter_chunked(bf, *fi, t->r, chunk, o, st, t->cus, IterQuit::none());
+            e = launch_find_iter_chunked(bf, *fi, t->r, chunk, o, st, t->cus, IterQuit::none(), nullptr, rag);
           }
           if (qf) {
             const hipError_t e2 = scratch_free(qf, st);
@@ -646,7 +726,8 @@ hipError_t run_find_iter(rure *re, DevTables *t, const BatchDev &b, const IterOu
           return e;
         }
         bool q = false;
-        const hipError_t e = launch_find_iter_chunked(b, *fa, t->r, chunk, o, st, t->cus, IterQuit::read_back(&q));
+        const hipError_t e =
+            launch_find_iter_chunked(b, *fa, t->r, chunk, o, st, t->cus, IterQuit::read_back(&q), nullptr, rag);
         if (e != hipSuccess || !q) {
           if (e == hipSuccess) note_fwd_path(RURE_AMD_PATH_ITER_SHADOW);
           return e;
@@ -660,12 +741,14 @@ hipError_t run_find_iter(rure *re, DevTables *t, const BatchDev &b, const IterOu
     // nothing read back).  Spans, and knob iter_wave=0, keep the read-back of
     // the quit and the one-wave-per-haystack fallback.
     if (fi->can_quit && !sp && re->nfa_ok && knob(Knob::IterWave) != 0) {
-      const hipError_t e = launch_find_iter_chunked(b, *fi, t->r, chunk, o, st, t->cus, IterQuit::wave_served(&t->n));
+      const hipError_t e =
+          launch_find_iter_chunked(b, *fi, t->r, chunk, o, st, t->cus, IterQuit::wave_served(&t->n), nullptr, rag);
       if (e == hipSuccess) note_fwd_path(RURE_AMD_PATH_ITER_WAVE_SERVED);
       return e;
     }
     bool quit = false;
-    const hipError_t e = launch_find_iter_chunked(b, *fi, t->r, chunk, o, st, t->cus, IterQuit::read_back(&quit), sp);
+    const hipError_t e =
+        launch_find_iter_chunked(b, *fi, t->r, chunk, o, st, t->cus, IterQuit::read_back(&quit), sp, rag);
     if (e == hipSuccess) {
       if (looks)
         note_fwd_path(quit ? RURE_AMD_PATH_ITER_LOOKS_QUIT : RURE_AMD_PATH_ITER_LOOKS);

@@ -19,7 +19,7 @@ const char *const kNames[kN] = {
     "lit",        "sa",          "lex",        "lex4",       "lex_tail",   "kmer",       "runs",
     "ascii_shadow", "fb",        "prefix",     "big",        "big_bytes",  "lazy",       "lazy_rows",
     "lines",      "split",       "suffix_long", "suffix_iter", "iter_looks", "iter_chunk", "iter_lanes",
-    "iter_bs",    "long_lanes",  "core_bs",    "core_lds",   "core_prof",  "scratch_cap", "timing",
+    "iter_ragged", "iter_bs",    "long_lanes",  "core_bs",    "core_lds",   "core_prof",  "scratch_cap", "timing",
     "replace_generic", "chain_seq", "shadow_sync", "iter_wave", "wave_cu", "wave_split", "wave_tables", "wave_lds",
 };
 

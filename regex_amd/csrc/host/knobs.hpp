@@ -30,6 +30,7 @@ enum class Knob : int {
   IterLooks,       // 0: look-around regexes' find_iter on the wave path
   IterChunk,       // find_iter unit size in bytes
   IterLanes,       // find_iter lanes per CU
+  IterRagged,      // 0: offset batches always one find_iter unit per haystack; 2: cut into iter_chunk units at any length
   IterBs,          // find_iter block size
   LongLanes,       // long-scan lanes per CU
   CoreBs,          // core-form set kernel block size

@@ -431,10 +431,24 @@ struct IterQuit {
   static IterQuit device_word(uint32_t *word) { IterQuit q; q.kind = DeviceWord; q.word = word; return q; }
   static IterQuit wave_served(const NfaDev *nfa) { IterQuit q; q.kind = WaveServed; q.nfa = nfa; return q; }
 };
-// The chunked speculative find_iter (iter_scan.hip): units of `chunk` bytes.
+// Ragged unit geometry of an offset batch (iter_device.hpp Geo::uoff):
+// haystack h, searched over span_h = max(0, len_h - start) bytes, has
+// max(1, ceil(span_h / chunk)) units.
+struct IterRagged {
+  const uint64_t *uoff;  // device, count + 1: exclusive sums of the units per haystack
+  uint64_t nunits;       // uoff[count], read back by the caller
+  uint64_t total;        // the sum of the spans (sizes the slots per unit)
+};
+// stats (device, 2 u64) = the longest span of an offset batch and the spans' sum.
+hipError_t launch_iter_span_stats(const BatchDev &b, uint64_t *stats, hipStream_t st, int cus);
+// nk (device scratch, count + 1) = the units per haystack, uoff = their exclusive sums.
+hipError_t launch_iter_ragged_units(const BatchDev &b, uint64_t chunk, uint64_t *nk, uint64_t *uoff, hipStream_t st);
+// The chunked speculative find_iter (iter_scan.hip): units of `chunk` bytes;
+// rag: an offset batch in its ragged geometry (built with the same chunk; no
+// span), else one unit per haystack of an offset batch.
 hipError_t launch_find_iter_chunked(const BatchDev &b, const FwdDfaDev &f, const RevDfaDev &r, uint64_t chunk,
                                     const IterOut &o, hipStream_t st, int cus, const IterQuit &quit,
-                                    const IterSpan *span = nullptr);
+                                    const IterSpan *span = nullptr, const IterRagged *rag = nullptr);
 // The k-mer probe engine of launch_find_iter_multi: the regexes' strings all
 // have one length len <= 8 over an alphabet of at most 4 bytes whose codes
 // (b >> shift) & 3 are distinct.  bitmap: 2048 u32, bit c set iff the L-mer
@@ -495,6 +509,10 @@ hipError_t launch_lit_find(int mode, const BatchDev &b, const FwdDfaDev &f, void
 // it, tests and the bench assert it.
 int last_fwd_path();
 void note_fwd_path(rure_amd_path path);
+// The units and haystacks of the last launch_find_iter_chunked of this
+// process (rure_amd_last_iter_units; 0, 0 before the first).
+uint64_t last_iter_units(uint64_t *haystacks);
+void note_iter_units(uint64_t units, uint64_t haystacks);
 // Kernel timer (rure_amd_kernel_timer): HIP event pairs around bracketed launches.
 void ktimer_begin(hipStream_t st);
 void ktimer_end(hipStream_t st);

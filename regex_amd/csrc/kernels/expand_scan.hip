@@ -26,6 +26,7 @@
 #include <algorithm>
 
 #include "dfa_scan.hpp"
+#include "iter_device.hpp"  // owner_of
 
 namespace rure_amd {
 
@@ -44,16 +45,6 @@ __device__ __forceinline__ void hay_at(const BatchDev &bt, uint64_t h, const uin
     *base = bt.hay + h * bt.stride;
     *len = bt.length;
   }
-}
-
-// The last i in [0, n] with a[i] <= x (a non-decreasing, n + 1 entries, a[0] <= x).
-__device__ __forceinline__ uint64_t owner_of(const uint64_t *a, uint64_t n, uint64_t x) {
-  uint64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint64_t mid = (lo + hi + 1) >> 1;
-    if (a[mid] <= x) lo = mid; else hi = mid - 1;
-  }
-  return lo;
 }
 
 __device__ __forceinline__ uint64_t min_u64(uint64_t a, uint64_t b) { return a < b ? a : b; }

@@ -2,7 +2,9 @@
 // exec.rs:473-514) for gfx950.
 //
 // The iteration is sequential by nature: each search starts where the
-// previous match ended.  Long haystacks are cut into chunks ("units"); one
+// previous match ended.  Long haystacks are cut into chunks ("units": the
+// same number per haystack of a fixed-stride batch, by each haystack's own
+// length in an offset batch, iter_device.hpp Geo); one
 // lane iterates each unit *speculatively* from a fresh start at the unit's
 // first byte, owning the matches that start inside it.  For patterns without
 // look-around assertions, a unit's speculative result is exact unless the
@@ -506,11 +508,12 @@ __global__ __launch_bounds__(1024) void iter_spec_burst_kernel(BatchDev b, Geo g
       U.spec_count = n;
       // (a unit after a byte >= 0x80 is unsure too when the DFA can quit: a
       // search from before its start reads that byte and quits, the fresh
-      // one at c0 reads it as a non-word byte, dfa.rs:1423)
-      const bool pre = f.can_quit == 2 && c0 > 0 && base[c0 - 1] >= 0x80;
+      // one at c0 reads it as a non-word byte, dfa.rs:1423; c0 <= len: a
+      // haystack shorter than `start` has no byte there)
+      const bool pre = f.can_quit == 2 && c0 > 0 && c0 <= len && base[c0 - 1] >= 0x80;
       // (a resumed unit stays U_QUIT: one of its searches ran on the Pike VM)
       U.flags = (clean ? (U_SPEC_CLEAN | U_CLEAN) : 0) | (quit ? U_QUIT : 0) | (quit && (mode & 1) ? U_PEND : 0) |
-                ((mode & 2) ? U_QUIT : 0) | (((f.looks && unsure) || pre) && u % g.nk != 0 ? U_UNSURE : 0);
+                ((mode & 2) ? U_QUIT : 0) | (((f.looks && unsure) || pre) && !unit_head(g, b, u) ? U_UNSURE : 0);
       U.skip = 0;
       U.pad = quit && qfirst ? 1 : 0;  // (a quit unit: its exit is the state before the search that quit)
       units[u] = U;
@@ -601,7 +604,8 @@ __global__ __launch_bounds__(1024) void iter_spec_lit_kernel(BatchDev b, Geo g, 
 // to c1 + L - 1, so it sees every string starting before its cut; blocks whose
 // OR of final bits is zero (almost all) take no per-byte branch.  Same unit
 // records as iter_spec_lit_kernel.
-template <typename W>
+// RAGGED: the batch's geometry may be the ragged one (unit_bounds).
+template <typename W, bool RAGGED>
 __global__ __launch_bounds__(256) void iter_spec_sa_kernel(BatchDev b, Geo g, uint64_t nunits, FwdDfaDev f,
                                                            Unit *units, uint64_t *slots, uint32_t *counts,
                                                            uint32_t *dirty) {
@@ -614,7 +618,7 @@ __global__ __launch_bounds__(256) void iter_spec_sa_kernel(BatchDev b, Geo g, ui
   for (uint64_t u = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; u < nunits; u += (uint64_t)gridDim.x * blockDim.x) {
     uint64_t h, len, c0, c1;
     const uint8_t *base;
-    unit_bounds(b, g, u, &h, &base, &len, &c0, &c1);
+    unit_bounds<RAGGED>(b, g, u, &h, &base, &len, &c0, &c1);
     uint64_t p = c0, lm = NONE;
     uint32_t n = 0;
     const uint64_t qend = c1 >= len ? len : min(len, c1 + L - 1);  // last bytes q < qend
@@ -1762,7 +1766,7 @@ __device__ bool repair_unit(const BatchDev &b, const Geo &g, const FwdDfaDev &f,
   Unit U = units[j];
   const bool spec_clean = (U.flags & U_SPEC_CLEAN) != 0;
   // the next unit's speculation is unsure: exits compare as states
-  const bool strict = f.looks && (j + 1) % g.nk != 0 && (units[j + 1].flags & U_UNSURE);
+  const bool strict = f.looks && !unit_tail(g, b, j) && (units[j + 1].flags & U_UNSURE);
   U.entry = E;
   U.flags = (U.flags & ~(U_COPY | U_CLEAN)) | U_FIXED;
   U.skip = 0;
@@ -1846,7 +1850,7 @@ __device__ __forceinline__ void fix_body(const BatchDev &b, const Geo &g, uint64
   bool staged = false;
   for (uint64_t u0 = (uint64_t)blockIdx.x * blockDim.x; u0 + 1 < nunits; u0 += (uint64_t)gridDim.x * blockDim.x) {
     const uint64_t u = u0 + threadIdx.x;
-    const bool need = u + 1 < nunits && (u + 1) % g.nk != 0 &&
+    const bool need = u + 1 < nunits && !unit_tail(g, b, u) &&
                       (!(units[u].flags & U_SPEC_CLEAN) || (units[u + 1].flags & U_UNSURE));
     if (!__syncthreads_or(need)) continue;
     if (!staged) {
@@ -1895,7 +1899,7 @@ __device__ __forceinline__ void walk_body(const BatchDev &b, const Geo &g, uint6
     if (j + 1 <= walked) continue;
     uint64_t u = j + 1;
     Unit X = units[j];
-    while (u < nunits && u % g.nk != 0) {
+    while (u < nunits && !unit_head(g, b, u)) {
       const Unit V = units[u];
       // entry the parallel passes assumed for unit u
       const Unit P = units[u - 1];
@@ -2059,14 +2063,14 @@ __global__ __launch_bounds__(512) void iter_wspec_kernel(BatchDev b, Geo g, uint
       if (lane == 0) units[u] = V;
       continue;
     }
-    const bool pre = f.can_quit == 2 && c0 > 0 && base[c0 - 1] >= 0x80;  // (as iter_spec_burst_kernel)
+    const bool pre = f.can_quit == 2 && c0 > 0 && c0 <= len && base[c0 - 1] >= 0x80;  // (as iter_spec_burst_kernel)
     const bool unsure = (U.pad != 0 ? f.looks && it.unsure : (U.flags & U_UNSURE) != 0) || pre;
     Unit V;
     V.entry = {c0, NONE};
     V.exit = it.exit;
     V.spec_exit = it.exit;
     V.spec_count = n;
-    V.flags = (it.clean ? (U_SPEC_CLEAN | U_CLEAN) : 0) | U_QUIT | (unsure && u % g.nk != 0 ? U_UNSURE : 0);
+    V.flags = (it.clean ? (U_SPEC_CLEAN | U_CLEAN) : 0) | U_QUIT | (unsure && !unit_head(g, b, u) ? U_UNSURE : 0);
     V.skip = V.pad = 0;
     if (lane == 0) {
       units[u] = V;
@@ -2090,7 +2094,7 @@ __global__ __launch_bounds__(512) void iter_wfix_kernel(BatchDev b, Geo g, uint6
   const WaveCtx wc{&S.nf, &S.W, &tg};
   for (uint64_t u = S.wave; u + 1 < nunits; u += S.nwaves) {
     const uint32_t fn = units[u + 1].flags;
-    const bool need = (u + 1) % g.nk != 0 && (fn & U_QUIT) &&
+    const bool need = !unit_tail(g, b, u) && (fn & U_QUIT) &&
                       (!(units[u].flags & U_SPEC_CLEAN) || (fn & U_UNSURE));
     if (!need) continue;
     const bool ch = repair_unit(b, g, f, r, f.lds_image, nullptr, u + 1, units[u].spec_exit, units, counts, slots, &wc);
@@ -2157,7 +2161,7 @@ __global__ void iter_entry_kernel(BatchDev b, Geo g, uint64_t nunits, FwdDfaDev 
   if (threadIdx.x != 0 || blockIdx.x != 0 || entry[2]) return;
   if (repair_unit(b, g, f, r, f.lds_image /* unused: hot = 0 */, nullptr, 0, IterSt{entry[0], entry[1]}, units,
                   counts, slots) &&
-      g.nk > 1) {
+      (g.nk > 1 || g.uoff)) {
     const unsigned long long q = atomicAdd(qlen, 1ull);
     queue[q] = 0;
   }
@@ -2538,17 +2542,69 @@ __global__ __launch_bounds__(64) void iter_wave_kernel(BatchDev b, FwdDfaDev f, 
   }
 }
 
-// counts[h] = matches of haystack h, total = all matches.
-__device__ __forceinline__ void counts_body(uint64_t nh, uint64_t nk, const uint64_t *off, uint64_t *hcounts,
-                                            uint64_t *total) {
+// counts[h] = matches of haystack h, total = all matches (uoff: Geo's).
+__device__ __forceinline__ void counts_body(uint64_t nh, uint64_t nk, const uint64_t *uoff, const uint64_t *off,
+                                            uint64_t *hcounts, uint64_t *total) {
   for (uint64_t h = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; h < nh; h += (uint64_t)gridDim.x * blockDim.x)
-    hcounts[h] = off[(h + 1) * nk] - off[h * nk];
-  if (blockIdx.x == 0 && threadIdx.x == 0) *total = off[nh * nk] - off[0];
+    hcounts[h] = uoff ? off[uoff[h + 1]] - off[uoff[h]] : off[(h + 1) * nk] - off[h * nk];
+  if (blockIdx.x == 0 && threadIdx.x == 0) *total = off[uoff ? uoff[nh] : nh * nk] - off[0];
 }
-__global__ void iter_counts_kernel(uint64_t nh, uint64_t nk, const uint64_t *off, uint64_t *hcounts,
-                                   uint64_t *total, BatchDev b) {
+__global__ void iter_counts_kernel(uint64_t nh, uint64_t nk, const uint64_t *uoff, const uint64_t *off,
+                                   uint64_t *hcounts, uint64_t *total, BatchDev b) {
   if (gated_off(b)) return;
-  counts_body(nh, nk, off, hcounts, total);
+  counts_body(nh, nk, uoff, off, hcounts, total);
+}
+
+// The searched bytes of haystack h of an offset batch.
+__device__ __forceinline__ uint64_t offs_span(const BatchDev &b, uint64_t h) {
+  const uint64_t len = b.offs[h + 1] - b.offs[h];
+  return len > b.start ? len - b.start : 0;
+}
+
+// stats[0] = the longest span of an offset batch's haystacks, stats[1] = the
+// spans' sum (stats zeroed by the launcher): per lane, per wave, per block, then
+// one atomic pair per block.
+__global__ __launch_bounds__(256) void iter_span_stats_kernel(BatchDev b, unsigned long long *stats) {
+  __shared__ uint64_t wmx[4], wsum[4];
+  uint64_t mx = 0, sum = 0;
+  for (uint64_t h = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; h < b.count; h += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t s = offs_span(b, h);
+    mx = max(mx, s);
+    sum += s;
+  }
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    mx = max(mx, (uint64_t)__shfl_xor(mx, d));
+    sum += (uint64_t)__shfl_xor(sum, d);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    wmx[threadIdx.x >> 6] = mx;
+    wsum[threadIdx.x >> 6] = sum;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (uint32_t w = 1; w < (blockDim.x >> 6); ++w) {
+      mx = max(mx, wmx[w]);
+      sum += wsum[w];
+    }
+    if (sum) {
+      atomicMax(&stats[0], (unsigned long long)mx);
+      atomicAdd(&stats[1], (unsigned long long)sum);
+    }
+  }
+}
+
+// Units per haystack of the ragged geometry (entry count = 0, so that the
+// exclusive scan's entry count is the number of units): at least one each.
+__global__ __launch_bounds__(256) void iter_ragged_units_kernel(BatchDev b, uint64_t chunk, uint64_t *nk) {
+  const uint64_t h = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (h > b.count) return;
+  uint64_t v = 0;
+  if (h < b.count) {
+    const uint64_t s = offs_span(b, h);
+    v = s <= chunk ? 1 : (s + chunk - 1) / chunk;
+  }
+  nk[h] = v;
 }
 
 hipError_t scan_counts(const uint32_t *counts, uint64_t *off, uint64_t n, hipStream_t st) {
@@ -2576,9 +2632,40 @@ static bool lex_usable(const FwdDfaDev &f, const BatchDev &b, const Geo &g) {
          b.length < (1ull << 32) && g.chunk <= 65536;
 }
 
+hipError_t launch_iter_span_stats(const BatchDev &b, uint64_t *stats, hipStream_t st, int cus) {
+  if (!b.offs) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(stats, 0, 16, st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(iter_span_stats_kernel, dim3(grid_cap(b.count, 256, cus, 4)), dim3(256), 0, st, b,
+                     (unsigned long long *)stats);
+  return hipGetLastError();
+}
+
+hipError_t launch_iter_ragged_units(const BatchDev &b, uint64_t chunk, uint64_t *nk, uint64_t *uoff, hipStream_t st) {
+  if (!b.offs || chunk == 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(iter_ragged_units_kernel, dim3((unsigned)((b.count + 1 + 255) / 256)), dim3(256), 0, st, b, chunk, nk);
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? e : exclusive_scan_u64(nk, uoff, b.count + 1, st);
+}
+
 // Unit geometry of a chunked find_iter: units of `chunk` bytes per haystack
-// (offset batches: one unit per haystack); returns the number of units.
-static uint64_t iter_geo(const BatchDev &b, uint64_t chunk, uint64_t hi, Geo *g) {
+// (offset batches: one unit per haystack, or rag's units of `chunk` bytes);
+// returns the number of units.
+static uint64_t iter_geo(const BatchDev &b, uint64_t chunk, uint64_t hi, Geo *g, const IterRagged *rag = nullptr) {
+  if (rag) {
+    g->nk = 1;
+    g->chunk = chunk;
+    g->end = hi;
+    g->uoff = rag->uoff;
+    // About a match per 256 bytes of the text, at least 16 and at most what a
+    // unit of this size keeps elsewhere: the slot scratch then stays at or
+    // below the text size even when a million short haystacks (a unit each)
+    // sit next to one long one; a unit with more matches is re-run by the
+    // emit pass.
+    const uint64_t per = rag->total / (16 * rag->nunits);
+    g->slots = (uint32_t)std::max<uint64_t>(16, std::min<uint64_t>(per, unit_slots(chunk)));
+    return rag->nunits;
+  }
   const uint64_t lim = std::min<uint64_t>(b.length, hi);
   const uint64_t span = (!b.offs && lim > b.start) ? lim - b.start : 0;
   g->chunk = chunk;
@@ -2687,7 +2774,7 @@ static hipError_t iter_post_body(const BatchDev &b, const Geo &g, uint64_t nunit
                        (const uint64_t *)sc.slots, spn->entry, sc.queue, sc.qlen);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
-  if (g.nk > 1) {
+  if (g.nk > 1 || g.uoff) {
     hipLaunchKernelGGL(iter_fix_kernel, dim3(grid), dim3(bs), lb, st, b, g, nunits, f, r, sc.units, sc.counts,
                        (const uint64_t *)sc.slots, sc.queue, sc.qlen, (const uint32_t *)sc.dirty);
     if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -2722,7 +2809,7 @@ static hipError_t iter_post_body(const BatchDev &b, const Geo &g, uint64_t nunit
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   hipLaunchKernelGGL(iter_counts_kernel, dim3(grid_cap(b.count, 256, cus, 4)), dim3(256), 0, st, b.count, g.nk,
-                     sc.off, o.counts, o.total, b);
+                     g.uoff, sc.off, o.counts, o.total, b);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if (spn && spn->exit) {
     hipLaunchKernelGGL(iter_exit_kernel, dim3(1), dim3(64), 0, st, (const Unit *)sc.units, nunits, spn->exit,
@@ -2856,7 +2943,7 @@ __global__ __launch_bounds__(1024) void multi_emit_kernel(BatchDev b, Geo g, uin
 
 __global__ void multi_counts_exit_kernel(BatchDev b, Geo g, uint64_t nunits, const PostDesc *d) {
   const PostDesc &P = d[blockIdx.y];
-  counts_body(b.count, g.nk, P.off, P.hcounts, P.total);
+  counts_body(b.count, g.nk, nullptr, P.off, P.hcounts, P.total);
   if (P.exit && blockIdx.x == 0 && threadIdx.x == 0) exit_body(P.units, nunits, P.exit, P.tail, P.nonempty);
 }
 
@@ -3005,7 +3092,8 @@ hipError_t launch_find_iter_multi(const BatchDev &b, int nre, const FwdDfaDev *c
 
 hipError_t launch_find_iter_chunked(const BatchDev &b, const FwdDfaDev &f, const RevDfaDev &r, uint64_t chunk,
                                     const IterOut &o, hipStream_t st, int cus, const IterQuit &quit,
-                                    const IterSpan *spn) {
+                                    const IterSpan *spn, const IterRagged *rag) {
+  if (rag && (!b.offs || spn || !rag->uoff || rag->nunits < b.count)) return hipErrorInvalidValue;
   bool ok = false;
   switch (quit.kind) {
     case IterQuit::None: ok = !f.can_quit; break;  // else nothing would write the quit units' matches
@@ -3021,7 +3109,8 @@ hipError_t launch_find_iter_chunked(const BatchDev &b, const FwdDfaDev &f, const
   hipError_t e = hipSuccess;
   if (b.count == 0) return hipMemsetAsync(o.total, 0, 8, st);
   Geo g;
-  const uint64_t nunits = iter_geo(b, chunk, spn ? spn->hi : ~0ull, &g);
+  const uint64_t nunits = iter_geo(b, chunk, spn ? spn->hi : ~0ull, &g, rag);
+  note_iter_units(nunits, b.count);
   // Dense matches: the caller's capacity tells how many to expect; slots
   // that hold them spare the emit pass re-running every unit (\b\w+\b over
   // English, ~750 matches per 4 KiB unit: 128 slots re-ran them all, 19 of
@@ -3086,8 +3175,10 @@ hipError_t launch_find_iter_chunked(const BatchDev &b, const FwdDfaDev &f, const
       else spec(iter_spec_sa_tile_kernel<uint64_t>, sg, dim3(256), 0, dirty);
     } else if (use_sa) {
       const dim3 sg(grid_cap(nunits, 256, cus, 8));
-      if (f.sa_bits <= 32) spec(iter_spec_sa_kernel<uint32_t>, sg, dim3(256), 0, dirty);
-      else spec(iter_spec_sa_kernel<uint64_t>, sg, dim3(256), 0, dirty);
+      if (f.sa_bits <= 32 && rag) spec(iter_spec_sa_kernel<uint32_t, true>, sg, dim3(256), 0, dirty);
+      else if (f.sa_bits <= 32) spec(iter_spec_sa_kernel<uint32_t, false>, sg, dim3(256), 0, dirty);
+      else if (rag) spec(iter_spec_sa_kernel<uint64_t, true>, sg, dim3(256), 0, dirty);
+      else spec(iter_spec_sa_kernel<uint64_t, false>, sg, dim3(256), 0, dirty);
     } else if (use_lit) {
       const dim3 lg(grid_cap(nunits, bs, cus, 2048 / bs));
       if (f.lit_k8) spec(iter_spec_lit_kernel<true, true>, lg, dim3(bs), kLitImage, dirty);
@@ -3187,7 +3278,7 @@ hipError_t launch_find_iter_wave(const BatchDev &b, const FwdDfaDev *f, const Re
                        spn ? spn->entry : (const uint64_t *)nullptr, hi, (uint64_t *)nullptr, md);
     if ((e = hipGetLastError()) != hipSuccess) break;
     hipLaunchKernelGGL(iter_counts_kernel, dim3(grid_cap(b.count, 256, cus, 4)), dim3(256), 0, st, b.count,
-                       (uint64_t)1, off, o.counts, o.total, b);
+                       (uint64_t)1, (const uint64_t *)nullptr, off, o.counts, o.total, b);
     e = hipGetLastError();
   } while (false);
   hipError_t e2 = scratch_free(buf, st);

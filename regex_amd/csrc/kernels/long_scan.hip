@@ -27,7 +27,7 @@ __global__ __launch_bounds__(256) void long_scan_kernel(BatchDev b, Geo g, uint6
   for (uint64_t u = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; u < nunits; u += (uint64_t)gridDim.x * blockDim.x) {
     uint64_t h, len, c0, c1;
     const uint8_t *base;
-    unit_bounds(b, g, u, &h, &base, &len, &c0, &c1);
+    unit_bounds<false>(b, g, u, &h, &base, &len, &c0, &c1);
     LaneState L;
     lane_start(L, f, base, len, c0);
     if (c1 > c0 && c1 - 1 <= len) {

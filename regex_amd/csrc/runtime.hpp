@@ -242,6 +242,7 @@ struct rure {
   Staging stage;
   // find_iter: forward DFA with dotstar-stripped states (chunked iteration)
   bool iter_built = false, iter_ok = false;
+  bool suffix_fwd = false;  // a DfaSuffix regex whose find_iter is the forward DFA's (build.cpp suffix_only_at_end)
   DenseDfa dfwd_iter;
   PackedFwd pf_iter;
   bool lit_ok = false;      // the regex is a finite string set (literal find_iter engine)
