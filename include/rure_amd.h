@@ -133,6 +133,19 @@ typedef struct rure_amd_batch {
   size_t start;
 } rure_amd_batch;
 
+/* The three calls below, for a regex whose DFA kernels answer: they only
+ * enqueue work on `stream`, never wait for it and read nothing back.  Few
+ * long fixed-stride haystacks (256 KiB or more to search) are scanned in
+ * parallel chunks.  So are, still without a wait, the long haystacks of an
+ * offset batch (documents of their own lengths): the one-lane-per-haystack
+ * kernel leaves every haystack with 256 KiB or more to search on a device
+ * list, and a chunked scan of the listed haystacks follows on the device (a
+ * few launches that return at once when nothing was listed;
+ * rure_amd_last_long_units tells).  That holds for a regex whose forward DFA
+ * answers the search and cannot quit; RegexSets, regexes with a Unicode word
+ * boundary, of the DfaSuffix or anchored-start Literal match types, or
+ * anchored at the start keep one lane per haystack of an offset batch
+ * (end-anchored ones read only the match from the end). */
 /* Batched rure_find: out[i] = leftmost-first match, or {SIZE_MAX, SIZE_MAX}. */
 int rure_amd_find_batch(rure *re, const rure_amd_batch *batch, rure_match *out, void *stream);
 /* Batched rure_is_match: out[i] in {0, 1}. */
@@ -545,6 +558,15 @@ int rure_amd_last_fwd_path(void);
  * haystack means nothing was cut.  0 and *haystacks = 0 before the first such
  * launch. */
 uint64_t rure_amd_last_iter_units(uint64_t *haystacks);
+/* Diagnostics (host only, one value for the whole process likewise): the
+ * units the last find / is_match / shortest_match call over an offset batch
+ * cut its deferred long haystacks into; *haystacks (may be NULL) = how many
+ * haystacks it deferred to the chunked scan, *chunk (may be NULL) = the unit
+ * size in bytes.  All 0 before the first such call and when it deferred
+ * nothing.  The figures are made on the device (a kernel of the batched call
+ * writes them into a pinned host record): this call waits for the work that
+ * the batched call enqueued on its stream. */
+uint64_t rure_amd_last_long_units(uint64_t *haystacks, uint64_t *chunk);
 /* Debug-only overrides of the engine dispatch and launch geometry
  * (regex_amd/csrc/host/knobs.hpp lists them): replaces the whole override
  * table, read once per process from RURE_AMD_DEBUG, by spec

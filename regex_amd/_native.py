@@ -212,6 +212,21 @@ def last_iter_units():
     return int(units), int(n.value)
 
 
+rure_amd_last_long_units = _sig("rure_amd_last_long_units", ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
+                                ctypes.POINTER(ctypes.c_uint64))
+
+
+def last_long_units():
+    """(units, haystacks, chunk) of the deferred long scan of the last find /
+    is_match / shortest_match call over an offset batch: how many haystacks it
+    left to the chunked scan, the unit size in bytes and the units they were
+    cut into; (0, 0, 0) before the first such call and when nothing was
+    deferred.  Waits for that call's work."""
+    n, c = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    units = rure_amd_last_long_units(ctypes.byref(n), ctypes.byref(c))
+    return int(units), int(n.value), int(c.value)
+
+
 rure_amd_debug_set = _sig("rure_amd_debug_set", ctypes.c_int, ctypes.c_char_p)
 rure_amd_first_byte_export = _sig("rure_amd_first_byte_export", ctypes.c_int, VP, VP)
 rure_amd_lex_export = _sig("rure_amd_lex_export", ctypes.c_int64, VP, VP, c_size, VP)

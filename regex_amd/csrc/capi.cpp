@@ -428,10 +428,13 @@ int rure_amd_find_batch(rure *re, const rure_amd_batch *batch, rure_match *out, 
   DevTables *t = regex_device(re, &err);
   if (!t) return err.rfind("HIP", 0) == 0 ? RURE_AMD_ERR_HIP : RURE_AMD_ERR_DFA;
   if (const FwdDfaDev *lit = literal_engine(MODE_FIND, re, *t, b))
-    return launch_lit_find(MODE_FIND, b, *lit, out, (hipStream_t)stream) == hipSuccess ? RURE_AMD_OK : RURE_AMD_ERR_HIP;
+    return run_lit_find(MODE_FIND, re, b, *t, *lit, out, (hipStream_t)stream) == hipSuccess ? RURE_AMD_OK
+                                                                                           : RURE_AMD_ERR_HIP;
   int grid = grid_for(b.count, t->f.lds_bytes, t->cus);
   uint64_t chunk;
-  const FwdDfaDev *iter = long_batch(MODE_FIND, b, *t, &chunk) ? iter_device(re, *t, &err) : nullptr;
+  const FwdDfaDev *iter =
+      long_batch(MODE_FIND, b, *t, &chunk) ? iter_device(re, *t, &err) : ragged_long_iter(re, b, *t);
+  if (b.offs && !iter) note_long_none();
   if (run_regex(MODE_FIND, b, *t, out, (hipStream_t)stream, grid, iter) != hipSuccess) return RURE_AMD_ERR_HIP;
   return RURE_AMD_OK;
 }
@@ -470,11 +473,13 @@ int rure_amd_is_match_batch(rure *re, const rure_amd_batch *batch, uint8_t *out,
   DevTables *t = regex_device(re, &err);
   if (!t) return err.rfind("HIP", 0) == 0 ? RURE_AMD_ERR_HIP : RURE_AMD_ERR_DFA;
   if (const FwdDfaDev *lit = literal_engine(MODE_ISMATCH, re, *t, b))
-    return launch_lit_find(MODE_ISMATCH, b, *lit, out, (hipStream_t)stream) == hipSuccess ? RURE_AMD_OK
-                                                                                      : RURE_AMD_ERR_HIP;
+    return run_lit_find(MODE_ISMATCH, re, b, *t, *lit, out, (hipStream_t)stream) == hipSuccess ? RURE_AMD_OK
+                                                                                              : RURE_AMD_ERR_HIP;
   int grid = grid_for(b.count, t->f.lds_bytes, t->cus);
   uint64_t chunk;
-  const FwdDfaDev *iter = long_batch(MODE_ISMATCH, b, *t, &chunk) ? iter_device(re, *t, &err) : nullptr;
+  const FwdDfaDev *iter =
+      long_batch(MODE_ISMATCH, b, *t, &chunk) ? iter_device(re, *t, &err) : ragged_long_iter(re, b, *t);
+  if (b.offs && !iter) note_long_none();
   if (run_regex(MODE_ISMATCH, b, *t, out, (hipStream_t)stream, grid, iter) != hipSuccess) return RURE_AMD_ERR_HIP;
   return RURE_AMD_OK;
 }
@@ -488,7 +493,9 @@ int rure_amd_shortest_match_batch(rure *re, const rure_amd_batch *batch, size_t 
   if (!t) return err.rfind("HIP", 0) == 0 ? RURE_AMD_ERR_HIP : RURE_AMD_ERR_DFA;
   int grid = grid_for(b.count, t->f.lds_bytes, t->cus);
   uint64_t chunk;
-  const FwdDfaDev *iter = long_batch(MODE_SHORTEST, b, *t, &chunk) ? iter_device(re, *t, &err) : nullptr;
+  const FwdDfaDev *iter =
+      long_batch(MODE_SHORTEST, b, *t, &chunk) ? iter_device(re, *t, &err) : ragged_long_iter(re, b, *t);
+  if (b.offs && !iter) note_long_none();
   if (run_regex(MODE_SHORTEST, b, *t, end, (hipStream_t)stream, grid, iter) != hipSuccess) return RURE_AMD_ERR_HIP;
   return RURE_AMD_OK;
 }
@@ -1181,6 +1188,9 @@ int rure_amd_uses_dfa(rure *re) {
 
 int rure_amd_last_fwd_path(void) { return rure_amd::last_fwd_path(); }
 uint64_t rure_amd_last_iter_units(uint64_t *haystacks) { return rure_amd::last_iter_units(haystacks); }
+uint64_t rure_amd_last_long_units(uint64_t *haystacks, uint64_t *chunk) {
+  return rure_amd::last_long_units(haystacks, chunk);
+}
 int rure_amd_suffix_forward(rure *re) {
   if (!re) return RURE_AMD_ERR_ARG;
   return build_iter_dfa(re) && re->suffix_fwd ? 1 : 0;

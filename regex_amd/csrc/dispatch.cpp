@@ -25,6 +25,71 @@ void note_iter_units(uint64_t units, uint64_t haystacks) {
   g_iter_units[1] = haystacks;
 }
 
+// rure_amd_last_long_units: the deferred long scan's figures (haystacks,
+// chunk, units) are made on the device, so its geometry kernel writes them
+// into one pinned record of the process and each call records an event behind
+// its kernels; the diagnostic waits for the event of the last call.
+namespace {
+struct LongRecord {
+  std::mutex mu;
+  uint64_t *host = nullptr;  // pinned, 3 words (allocated with the first call)
+  std::map<int, hipEvent_t> ev;  // per device
+  hipEvent_t last = nullptr;
+  bool none = true;  // the last such call deferred nothing (it took another path)
+};
+LongRecord &long_record() {
+  static LongRecord *r = new LongRecord();  // never destroyed: the runtime may be gone at exit
+  return *r;
+}
+}  // namespace
+
+// The record as the current device addresses it (allocated with the first call).
+hipError_t long_record_device(uint64_t **rec) {
+  LongRecord &r = long_record();
+  std::lock_guard<std::mutex> g(r.mu);
+  hipError_t e;
+  if (!r.host) {
+    if ((e = hipHostMalloc((void **)&r.host, 3 * sizeof(uint64_t), hipHostMallocPortable | hipHostMallocMapped)) !=
+        hipSuccess)
+      return e;
+    r.host[0] = r.host[1] = r.host[2] = 0;
+  }
+  return hipHostGetDevicePointer((void **)rec, r.host, 0);
+}
+
+hipError_t note_long_units(hipStream_t st) {
+  LongRecord &r = long_record();
+  std::lock_guard<std::mutex> g(r.mu);
+  hipError_t e;
+  int d = 0;
+  if ((e = hipGetDevice(&d)) != hipSuccess) return e;
+  hipEvent_t &ev = r.ev[d];
+  if (!ev && (e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return e;
+  r.last = ev;
+  r.none = false;
+  return hipEventRecord(ev, st);
+}
+
+void note_long_none() {
+  LongRecord &r = long_record();
+  std::lock_guard<std::mutex> g(r.mu);
+  r.none = true;
+}
+
+uint64_t last_long_units(uint64_t *haystacks, uint64_t *chunk) {
+  LongRecord &r = long_record();
+  std::lock_guard<std::mutex> g(r.mu);
+  if (r.none || !r.host) {
+    if (haystacks) *haystacks = 0;
+    if (chunk) *chunk = 0;
+    return 0;
+  }
+  (void)hipEventSynchronize(r.last);
+  if (haystacks) *haystacks = r.host[0];
+  if (chunk) *chunk = r.host[1];
+  return r.host[2];
+}
+
 }  // namespace rure_amd
 
 namespace rt {
@@ -298,6 +363,77 @@ static bool lazy_batch(const BatchDev &b, const DevTables &t) {
   return lazy_device(t);
 }
 
+// Offset batches (documents of their own lengths) of find / is_match /
+// shortest_match: one lane per haystack would walk a long document alone
+// (64 MiB: seconds), and the host knows no length without reading the offsets
+// back, which these calls never do (they only enqueue).  So the lane kernel
+// defers: a haystack whose span reaches 256 KiB (long_batch's threshold) goes
+// on a device list and gets "no match"; the chunk, the units and the chunked
+// scan of the listed haystacks follow on the device (launch_long_ragged),
+// empty launches when nothing was listed.  For a forward DFA that cannot
+// quit and has the find_iter automaton's strip table (an anchored-start regex
+// has none: its lanes die where the text stops matching).  Knobs long_ragged:
+// 0 never, 2 every haystack longer than one chunk; long_chunk: the chunk
+// floor (tests: cuts everywhere); long_list: the list's capacity.
+const FwdDfaDev *ragged_long_iter(rure *re, const BatchDev &b, const DevTables &t) {
+  if (!b.offs || !b.count || !t.has_dfa || t.quit_possible || t.anchored_rev || lane_search_ok(t)) return nullptr;
+  if (knob(Knob::LongRagged) == 0) return nullptr;
+  std::string err;
+  const FwdDfaDev *fi = iter_device(re, t, &err);
+  return fi && !re->dfwd_iter.strip.empty() ? fi : nullptr;
+}
+
+static uint64_t device_mem_cached() {
+  int d = 0;
+  (void)hipGetDevice(&d);
+  static std::mutex mu;
+  static std::map<int, uint64_t> cache;
+  std::lock_guard<std::mutex> g(mu);
+  auto it = cache.find(d);
+  if (it != cache.end()) return it->second;
+  hipDeviceProp_t prop;
+  const uint64_t bytes = hipGetDeviceProperties(&prop, d) == hipSuccess ? (uint64_t)prop.totalGlobalMem : 0;
+  return cache[d] = bytes ? bytes : 1ull << 40;
+}
+
+// lit: the literal engine is the lane kernel (iter is its image too).  The
+// scratch holds the list and the units' results for the most there can be:
+// no buffer of the device holds more than memory / threshold haystacks of
+// that length, and units <= listed + lanes (long_scan.hip).
+hipError_t run_ragged_long(int mode, const BatchDev &b, const DevTables &t, const FwdDfaDev &iter, bool lit, void *out,
+                           hipStream_t st, int dfa_grid) {
+  uint64_t per_cu = 1024;  // long_batch's lanes in flight
+  if (knob(Knob::LongLanes) > 0) per_cu = std::max<uint64_t>(64, knob(Knob::LongLanes));
+  const uint64_t lanes = (uint64_t)t.cus * per_cu;
+  const bool any = knob(Knob::LongRagged) == 2;
+  const long long kc = knob(Knob::LongChunk);
+  const uint64_t floor = kc > 0 ? std::max<uint64_t>(16, kc) : 16u << 10;
+  const uint64_t least = any ? floor + 1 : 256u << 10;  // the span that defers
+  uint64_t cap = any ? b.count : std::min<uint64_t>(b.count, device_mem_cached() / least);
+  if (knob(Knob::LongList) > 0) cap = std::min<uint64_t>(cap, knob(Knob::LongList));
+  cap = std::max<uint64_t>(cap, 1);
+  BatchDev bd = b;
+  bd.defer_len = b.start > ~0ull - least ? ~0ull : b.start + least;
+  uint64_t *rec = nullptr;
+  hipError_t e = long_record_device(&rec);
+  if (e != hipSuccess) return e;
+  if ((e = scratch_malloc((void **)&bd.defer, long_ragged_bytes(mode, cap, lanes), st)) != hipSuccess) return e;
+  e = launch_long_defer_init(bd.defer, cap, st);
+  if (e == hipSuccess)
+    e = lit ? launch_lit_find(mode, bd, iter, out, st) : launch_dfa_fwd(mode, bd, t.f, t.r, out, st, dfa_grid);
+  if (e == hipSuccess) e = launch_long_ragged(mode, bd, cap, iter, t.r, floor, kc <= 0, lanes, rec, out, st, t.cus);
+  if (e == hipSuccess) e = note_long_units(st);
+  const hipError_t e2 = scratch_free(bd.defer, st);
+  return e != hipSuccess ? e : e2;
+}
+
+hipError_t run_lit_find(int mode, rure *re, const BatchDev &b, const DevTables &t, const FwdDfaDev &lit, void *out,
+                        hipStream_t st) {
+  if (ragged_long_iter(re, b, t)) return run_ragged_long(mode, b, t, lit, true, out, st, 0);
+  if (b.offs) note_long_none();
+  return launch_lit_find(mode, b, lit, out, st);
+}
+
 hipError_t run_regex(int mode, const BatchDev &b, const DevTables &t, void *out, hipStream_t st, int dfa_grid,
                      const FwdDfaDev *iter) {
   if (lane_search_ok(t)) return run_lane_search(mode, b, t, out, st);
@@ -309,6 +445,8 @@ hipError_t run_regex(int mode, const BatchDev &b, const DevTables &t, void *out,
   uint64_t chunk = 0;
   if (iter && long_batch(mode, b, t, &chunk) && !(t.anchored_rev && b.start != 0))
     return launch_long_scan(mode, b, *iter, t.r, chunk, out, st, t.cus);
+  // an offset batch comes with the find_iter automaton only from ragged_long_iter
+  if (iter && b.offs) return run_ragged_long(mode, b, t, *iter, false, out, st, dfa_grid);
   if (!t.quit_possible) return run_dfa_step(mode, b, t, out, st, dfa_grid, nullptr);
   // the DFA kernels flag a quit; the Pike VM fallback returns at once without
   BatchDev bq = b;

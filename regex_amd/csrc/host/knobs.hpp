@@ -46,6 +46,9 @@ enum class Knob : int {
   WaveSplit,       // 0: those waves' stamps in scratch too, not in the LDS
   WaveTables,      // 0: no NFA tables staged in the LDS for those waves
   WaveLds,         // 1: those waves' whole working set in the LDS, however few waves fit
+  LongRagged,      // 0: offset batches of find / is_match / shortest_match one lane per haystack; 2: defer any haystack longer than a chunk
+  LongChunk,       // the chunk floor in bytes of that deferred long scan (no odd-lines rounding)
+  LongList,        // the capacity of its list of deferred haystacks
   kCount
 };
 

@@ -45,6 +45,23 @@ struct LaneState {
 static constexpr uint64_t NONE = ~0ull;
 static constexpr uint64_t QUITMARK = ~0ull - 1;
 
+// Whether haystack h (len bytes) of an offset batch is left to the deferred
+// long scan (BatchDev::defer): appended to the list, its span added to the
+// total.  False: the lane scans it (no deferral, a short span, a full list).
+// The kernels that defer are instances of their own (DEFER), so the others
+// stay as they were.  The arguments are kept to a pointer and a length (the
+// capacity sits in the header): with three words and the test compiled into
+// the one instance, the line kernel's find form took 106 SGPRs for 99 and the
+// offsets stream kernel a VGPR more, a wave per SIMD each.
+__device__ __forceinline__ bool defer_long(const BatchDev &bt, uint64_t h, uint64_t len) {
+  if (len < bt.defer_len) return false;
+  const unsigned long long i = atomicAdd(&bt.defer[kDeferTried], 1ull);
+  if (i >= bt.defer[kDeferCap]) return false;
+  bt.defer[kDeferList + i] = h;
+  atomicAdd(&bt.defer[kDeferTotal], (unsigned long long)(len - bt.start));
+  return true;
+}
+
 // The descriptor with no hot rows: every step reads the global tables (for
 // kernels that stage no LDS image, or whose LDS holds something else).
 inline FwdDfaDev global_tables(FwdDfaDev f) { f.hot = 0; return f; }

@@ -68,7 +68,7 @@ __device__ __forceinline__ void finish_lane(const LaneState &L, const RevDfaDev 
   ((uint64_t *)out)[2 * h + 1] = me;
 }
 
-template <int MODE, bool STRIDED, bool PFX>
+template <int MODE, bool STRIDED, bool PFX, bool DEFER = false>
 __global__ __launch_bounds__(256) void dfa_fwd_kernel(BatchDev bt, FwdDfaDev f, RevDfaDev r, void *out) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   for (uint32_t i = threadIdx.x * 16; i < f.lds_bytes; i += blockDim.x * 16)
@@ -89,6 +89,9 @@ __global__ __launch_bounds__(256) void dfa_fwd_kernel(BatchDev bt, FwdDfaDev f, 
     }
     LaneState L;
     lane_start(L, f, base, len, bt.start);
+    // a long haystack of an offset batch: left to the deferred long scan,
+    // "no match" written here (a done lane scans nothing)
+    if (DEFER && defer_long(bt, h, len)) L.done = true;
     fwd_run<MODE, PFX>(L, f, lds, base, len, bt.start);
     finish_lane<MODE>(L, r, base, len, bt.start, h, out, bt.quit_flag);
   }
@@ -165,7 +168,7 @@ double ktimer_read(uint64_t *launches) {
 // literal occurs: the leftmost start, and there the first literal in priority
 // order is the leftmost-first match.  No reverse scan: the literal's length
 // gives the end.
-template <int MODE, bool STRIDED, bool K4, bool K8>
+template <int MODE, bool STRIDED, bool K4, bool K8, bool DEFER = false>
 __global__ __launch_bounds__(256) void lit_find_kernel(BatchDev bt, FwdDfaDev f, void *out) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   for (uint32_t i = threadIdx.x * 16; i < f.lit_bytes; i += blockDim.x * 16)
@@ -189,7 +192,8 @@ __global__ __launch_bounds__(256) void lit_find_kernel(BatchDev bt, FwdDfaDev f,
     uint64_t ms = NONE, me = NONE;
     // candidate starts [start, iend): room for the shortest literal
     const uint64_t iend = len + 1 >= f.lit_minlen ? len + 1 - f.lit_minlen : 0;
-    if (iend > bt.start) {
+    // (a long haystack of an offset batch: left to the deferred long scan)
+    if (iend > bt.start && !(DEFER && defer_long(bt, h, len))) {
       const uintptr_t hi_blk = (uintptr_t)(base + len);
       const uintptr_t aend = (uintptr_t)(base + iend);
       for (uintptr_t a = (uintptr_t)(base + bt.start) & ~(uintptr_t)15; a < aend && ms == NONE; a += 64) {
@@ -217,15 +221,17 @@ __global__ __launch_bounds__(256) void lit_find_kernel(BatchDev bt, FwdDfaDev f,
   }
 }
 
-template <int MODE, bool STRIDED>
+template <int MODE, bool STRIDED, bool DEFER = false>
 static hipError_t launch_lit_find_m(const BatchDev &b, const FwdDfaDev &f, void *out, hipStream_t st, int grid) {
   if (f.lit_k8)
-    hipLaunchKernelGGL((lit_find_kernel<MODE, STRIDED, true, true>), dim3(grid), dim3(256), kLitImage, st, b, f, out);
-  else if (f.lit_k == 4)
-    hipLaunchKernelGGL((lit_find_kernel<MODE, STRIDED, true, false>), dim3(grid), dim3(256), kLitImage, st, b, f, out);
-  else
-    hipLaunchKernelGGL((lit_find_kernel<MODE, STRIDED, false, false>), dim3(grid), dim3(256), kLitImage, st, b, f,
+    hipLaunchKernelGGL((lit_find_kernel<MODE, STRIDED, true, true, DEFER>), dim3(grid), dim3(256), kLitImage, st, b, f,
                        out);
+  else if (f.lit_k == 4)
+    hipLaunchKernelGGL((lit_find_kernel<MODE, STRIDED, true, false, DEFER>), dim3(grid), dim3(256), kLitImage, st, b, f,
+                       out);
+  else
+    hipLaunchKernelGGL((lit_find_kernel<MODE, STRIDED, false, false, DEFER>), dim3(grid), dim3(256), kLitImage, st, b,
+                       f, out);
   return hipGetLastError();
 }
 
@@ -235,6 +241,9 @@ hipError_t launch_lit_find(int mode, const BatchDev &b, const FwdDfaDev &f, void
   const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)f.cus * 32));
   note_fwd_path(RURE_AMD_PATH_LITERAL);
   const bool strided = b.offs == nullptr;
+  if (!strided && b.defer)  // an offset batch with the deferred long scan
+    return mode == MODE_FIND ? launch_lit_find_m<MODE_FIND, false, true>(b, f, out, st, grid)
+                             : launch_lit_find_m<MODE_ISMATCH, false, true>(b, f, out, st, grid);
   if (mode == MODE_FIND)
     return strided ? launch_lit_find_m<MODE_FIND, true>(b, f, out, st, grid)
                    : launch_lit_find_m<MODE_FIND, false>(b, f, out, st, grid);
@@ -879,7 +888,7 @@ __host__ __device__ inline uint32_t line_lds_total(int mode, uint32_t f_bytes, u
   return line_rev_off(f_bytes) + (mode == MODE_FIND ? ((r_bytes + 15) & ~15u) : 0u);
 }
 
-template <int MODE>
+template <int MODE, bool DEFER = false>
 __global__ __launch_bounds__(1024) void dfa_line_kernel(BatchDev bt, FwdDfaDev f, RevDfaDev r, void *out) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   for (uint32_t i = threadIdx.x * 16; i < f.lds_bytes; i += blockDim.x * 16)
@@ -941,6 +950,9 @@ __global__ __launch_bounds__(1024) void dfa_line_kernel(BatchDev bt, FwdDfaDev f
       }
       if (L.s >= f.n_normal) L.done = true;  // dead start state (dfa.rs:484)
     }
+    // a long line: left to the deferred long scan, "no match" written here
+    // (a done lane scans nothing and still issues the next lines' loads)
+    if (DEFER && defer_long(bt, h, len)) L.done = true;
     uint4 cur = x0;
     if (!L.done && at < len && k0) {  // head: the rest of one aligned block
       const uint32_t kend = len - at < 16 - k0 ? k0 + (uint32_t)(len - at) : 16;
@@ -961,7 +973,8 @@ __global__ __launch_bounds__(1024) void dfa_line_kernel(BatchDev bt, FwdDfaDev f
     blocks(b0, b1, y0, y1);
     if (!L.done && at < len) line_block<MODE, true>(L, f, lds, cur, at, 0, (uint32_t)(len - at));
     if (!L.done && f.eof[L.s]) L.last = len;  // dfa.rs:748-763
-    finish_lane<MODE>(L, r, base, len, at0, h, out, bt.quit_flag, rlds);
+    // (the deferring instance serves DFAs that cannot quit: no flag to hold)
+    finish_lane<MODE>(L, r, base, len, at0, h, out, DEFER ? nullptr : bt.quit_flag, rlds);
     a0 = b0; a1 = b1; b0 = c0; b1 = c1; x0 = y0; x1 = y1;
   }
 }
@@ -981,7 +994,7 @@ static hipError_t launch_lines_m(const BatchDev &b, const FwdDfaDev &f, const Re
   const int per_cu = std::max<int>(1, std::min<int>(2, (int)((160u * 1024u) / lds)));
   const uint64_t blocks = (b.count + bs - 1) / bs;
   const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)f.cus * per_cu));
-  auto kern = dfa_line_kernel<MODE>;
+  auto kern = b.defer ? dfa_line_kernel<MODE, true> : dfa_line_kernel<MODE, false>;
   hipError_t e;
   if (lds > 64 * 1024 &&
       (e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess)
@@ -1056,7 +1069,11 @@ static hipError_t launch_fwd(const BatchDev &b, const FwdDfaDev &f, const RevDfa
   // no start-state prefix skip here: one lane per haystack, and the skip's
   // registers cost more than it saves on every pattern measured
   // (profiles/r03_prefix_ab.jsonl, "lines": 1.33 -> 1.81 ms for >[^\n]*\n)
-  hipLaunchKernelGGL((dfa_fwd_kernel<MODE, STRIDED, false>), dim3(grid), dim3(256), f.lds_bytes, st, b, f, r, out);
+  if (!STRIDED && b.defer)  // an offset batch with the deferred long scan
+    hipLaunchKernelGGL((dfa_fwd_kernel<MODE, false, false, true>), dim3(grid), dim3(256), f.lds_bytes, st, b, f, r,
+                       out);
+  else
+    hipLaunchKernelGGL((dfa_fwd_kernel<MODE, STRIDED, false>), dim3(grid), dim3(256), f.lds_bytes, st, b, f, r, out);
   return hipGetLastError();
 }
 

@@ -45,7 +45,21 @@ struct BatchDev {
   // set masks (the Pike VM's MODE_SET): words between consecutive haystacks'
   // masks (a set of more than 64 patterns: group g writes word g)
   uint32_t out_stride = 1;
+  // offset batches of find / is_match / shortest_match with the deferred long
+  // scan (long_scan.hip launch_long_ragged; nullptr: none): a lane whose
+  // haystack has defer_len bytes or more (the threshold on its span plus
+  // `start`) appends it to the list behind `defer` (kDefer* words; a full
+  // list leaves the haystack to the lane), writes "no match" and moves on
+  unsigned long long *defer = nullptr;
+  uint64_t defer_len = 0;
 };
+
+// The deferred long scan's device block (u64 words): the header, then the
+// list of deferred haystacks (kDeferCap entries).  kDeferTried counts the
+// lanes that asked (it may pass the capacity); the geometry kernel writes
+// kDeferCount .. kDeferUnits (and the same figures into the host's record
+// for rure_amd_last_long_units).
+enum { kDeferTried = 0, kDeferTotal = 1, kDeferCount = 2, kDeferChunk = 3, kDeferUnits = 4, kDeferCap = 5, kDeferList = 8 };
 
 // Forward DFA on the device.  State ids: [0, hot) are in the LDS fast table
 // (u8, 256 columns, row `hot` = absorbing sentinel); [0, n_normal) carry no
@@ -477,6 +491,28 @@ hipError_t launch_find_iter_multi(const BatchDev &b, int nre, const FwdDfaDev *c
 // (long_scan.hip); f must be the find_iter DFA (with strip).
 hipError_t launch_long_scan(int mode, const BatchDev &b, const FwdDfaDev &f, const RevDfaDev &r, uint64_t chunk,
                             void *out, hipStream_t st, int cus);
+
+// The same search over the long haystacks of an offset batch that the lane
+// kernels deferred (long_scan.hip): b.defer = the header that
+// launch_long_defer_init set (a list of `cap` haystacks) and the list the
+// lane kernel filled, in a block of long_ragged_bytes(mode, cap, lanes).  The
+// chunk is made on the device: max(floor, deferred bytes / lanes), rounded
+// with odd_lines if `round`; the units and the scan follow in fixed grids
+// (find's winner per haystack is written by its last unit to finish).  rec
+// (device-visible host memory, or null) receives the haystacks, the chunk and
+// the units.  Enqueues only.
+size_t long_ragged_bytes(int mode, uint64_t cap, uint64_t lanes);
+hipError_t launch_long_defer_init(unsigned long long *defer, uint64_t cap, hipStream_t st);
+hipError_t launch_long_ragged(int mode, const BatchDev &b, uint64_t cap, const FwdDfaDev &f, const RevDfaDev &r,
+                              uint64_t floor, bool round, uint64_t lanes, uint64_t *rec, void *out, hipStream_t st,
+                              int cus);
+// The haystacks, chunk and units of the last launch_long_ragged of this
+// process (rure_amd_last_long_units; dispatch.cpp): waits for the event the
+// call recorded behind its kernels.
+uint64_t last_long_units(uint64_t *haystacks, uint64_t *chunk);
+// A find / is_match / shortest_match call over an offset batch that took
+// another path: that diagnostic reads 0.
+void note_long_none();
 
 hipError_t launch_dfa_fwd(int mode, const BatchDev &b, const FwdDfaDev &f, const RevDfaDev &r, void *out,
                           hipStream_t st, int grid);

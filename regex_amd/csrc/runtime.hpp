@@ -375,6 +375,11 @@ hipError_t run_suffix_long(int mode, const BatchDev &b, const DevTables &t, uint
                            hipStream_t st);
 hipError_t run_lane_search(int mode, const BatchDev &b, const DevTables &t, void *out, hipStream_t st);
 bool big_batch(const BatchDev &b, const DevTables &t);
+const FwdDfaDev *ragged_long_iter(rure *re, const BatchDev &b, const DevTables &t);
+hipError_t run_ragged_long(int mode, const BatchDev &b, const DevTables &t, const FwdDfaDev &iter, bool lit, void *out,
+                           hipStream_t st, int dfa_grid);
+hipError_t run_lit_find(int mode, rure *re, const BatchDev &b, const DevTables &t, const FwdDfaDev &lit, void *out,
+                        hipStream_t st);
 hipError_t run_regex(int mode, const BatchDev &b, const DevTables &t, void *out, hipStream_t st, int dfa_grid,
                      const FwdDfaDev *iter = nullptr);
 hipError_t run_set(const BatchDev &b, const DevTables &t, uint64_t *out, hipStream_t st, int dfa_grid);
