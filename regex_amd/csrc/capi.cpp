@@ -72,11 +72,11 @@ bool captures_call(rure *re, const uint8_t *hay, size_t len, size_t start, uint6
   hipStream_t st = re->stage.stream;
   if (len && !hip_ok(hipMemcpyAsync(re->stage.hay, hay, len, hipMemcpyHostToDevice, st), &err)) die(err);
   BatchDev b{re->stage.hay, nullptr, len, len, 1, start};
-  uint64_t *dev = re->stage.res;
-  if (ns > 64 && !hip_ok(scratch_malloc((void **)&dev, (size_t)ns * 8, st), &err)) die(err);
+  Scratch<uint64_t> wide;  // more slots than the staging area's result holds
+  if (ns > 64 && !hip_ok(wide.alloc((size_t)ns * 8, st), &err)) die(err);
+  uint64_t *dev = wide ? wide.get() : re->stage.res;
   if (!hip_ok(run_captures(b, *t, dev, ns, st, 1), &err)) die(err);
   if (!hip_ok(hipMemcpyAsync(slots, dev, (size_t)ns * 8, hipMemcpyDeviceToHost, st), &err)) die(err);
-  if (dev != re->stage.res && !hip_ok(scratch_free(dev, st), &err)) die(err);
   if (!hip_ok(hipStreamSynchronize(st), &err)) die(err);
   if (slots[0] == kQuit || slots[1] == kQuit) die("internal error: unresolved DFA quit");
   return slots[0] != ~0ull && slots[1] != ~0ull;
@@ -421,22 +421,7 @@ bool rure_set_matches(rure_set *rs, const uint8_t *hay, size_t len, size_t start
 
 int rure_amd_find_batch(rure *re, const rure_amd_batch *batch, rure_match *out, void *stream) {
   static_assert(sizeof(rure_match) == 16, "rure_match layout");
-  BatchDev b;
-  if (!re || !to_batch(batch, &b) || (!out && b.count)) return RURE_AMD_ERR_ARG;
-  if (b.count == 0) return RURE_AMD_OK;
-  std::string err;
-  DevTables *t = regex_device(re, &err);
-  if (!t) return err.rfind("HIP", 0) == 0 ? RURE_AMD_ERR_HIP : RURE_AMD_ERR_DFA;
-  if (const FwdDfaDev *lit = literal_engine(MODE_FIND, re, *t, b))
-    return run_lit_find(MODE_FIND, re, b, *t, *lit, out, (hipStream_t)stream) == hipSuccess ? RURE_AMD_OK
-                                                                                           : RURE_AMD_ERR_HIP;
-  int grid = grid_for(b.count, t->f.lds_bytes, t->cus);
-  uint64_t chunk;
-  const FwdDfaDev *iter =
-      long_batch(MODE_FIND, b, *t, &chunk) ? iter_device(re, *t, &err) : ragged_long_iter(re, b, *t);
-  if (b.offs && !iter) note_long_none();
-  if (run_regex(MODE_FIND, b, *t, out, (hipStream_t)stream, grid, iter) != hipSuccess) return RURE_AMD_ERR_HIP;
-  return RURE_AMD_OK;
+  return search_batch(MODE_FIND, re, batch, out, (hipStream_t)stream);
 }
 
 int rure_amd_compact_matches(const rure_match *found, size_t n, uint64_t base, uint64_t *records, size_t capacity,
@@ -466,41 +451,12 @@ int rure_amd_captures_batch(rure *re, const rure_amd_batch *batch, size_t *slots
 }
 
 int rure_amd_is_match_batch(rure *re, const rure_amd_batch *batch, uint8_t *out, void *stream) {
-  BatchDev b;
-  if (!re || !to_batch(batch, &b) || (!out && b.count)) return RURE_AMD_ERR_ARG;
-  if (b.count == 0) return RURE_AMD_OK;
-  std::string err;
-  DevTables *t = regex_device(re, &err);
-  if (!t) return err.rfind("HIP", 0) == 0 ? RURE_AMD_ERR_HIP : RURE_AMD_ERR_DFA;
-  if (const FwdDfaDev *lit = literal_engine(MODE_ISMATCH, re, *t, b))
-    return run_lit_find(MODE_ISMATCH, re, b, *t, *lit, out, (hipStream_t)stream) == hipSuccess ? RURE_AMD_OK
-                                                                                              : RURE_AMD_ERR_HIP;
-  int grid = grid_for(b.count, t->f.lds_bytes, t->cus);
-  uint64_t chunk;
-  const FwdDfaDev *iter =
-      long_batch(MODE_ISMATCH, b, *t, &chunk) ? iter_device(re, *t, &err) : ragged_long_iter(re, b, *t);
-  if (b.offs && !iter) note_long_none();
-  if (run_regex(MODE_ISMATCH, b, *t, out, (hipStream_t)stream, grid, iter) != hipSuccess) return RURE_AMD_ERR_HIP;
-  return RURE_AMD_OK;
+  return search_batch(MODE_ISMATCH, re, batch, out, (hipStream_t)stream);
 }
 
 int rure_amd_shortest_match_batch(rure *re, const rure_amd_batch *batch, size_t *end, void *stream) {
-  BatchDev b;
-  if (!re || !to_batch(batch, &b) || (!end && b.count)) return RURE_AMD_ERR_ARG;
-  if (b.count == 0) return RURE_AMD_OK;
-  std::string err;
-  DevTables *t = regex_device(re, &err);
-  if (!t) return err.rfind("HIP", 0) == 0 ? RURE_AMD_ERR_HIP : RURE_AMD_ERR_DFA;
-  int grid = grid_for(b.count, t->f.lds_bytes, t->cus);
-  uint64_t chunk;
-  const FwdDfaDev *iter =
-      long_batch(MODE_SHORTEST, b, *t, &chunk) ? iter_device(re, *t, &err) : ragged_long_iter(re, b, *t);
-  if (b.offs && !iter) note_long_none();
-  if (run_regex(MODE_SHORTEST, b, *t, end, (hipStream_t)stream, grid, iter) != hipSuccess) return RURE_AMD_ERR_HIP;
-  return RURE_AMD_OK;
+  return search_batch(MODE_SHORTEST, re, batch, end, (hipStream_t)stream);
 }
-
-
 
 int rure_amd_set_matches_batch_words(rure_set *rs, const rure_amd_batch *batch, uint64_t *mask, size_t words,
                                      void *stream) {
@@ -640,11 +596,10 @@ int rure_amd_find_iter_span_multi(rure *const *res, size_t n, const uint8_t *hay
     sps[i] = IterSpan{hcut, entry ? (const uint64_t *)entry[i] : nullptr, (uint64_t *)exit[i], tail};
   }
   if (fused) {
-    // the unit size of run_find_iter (one haystack: the span over the lanes in flight)
+    // run_find_iter's unit for one haystack.  Kept from before: knob
+    // iter_chunk does not reach this path.
     const uint64_t span = std::min<uint64_t>(length, hcut) - lo;
-    uint64_t per_cu = 1024;
-    if (knob(Knob::IterLanes) > 0) per_cu = std::max<uint64_t>(64, knob(Knob::IterLanes));
-    const uint64_t chunk = odd_lines(std::max<uint64_t>(4096, (span + (uint64_t)cus * per_cu - 1) / ((uint64_t)cus * per_cu)));
+    const uint64_t chunk = unit_bytes(span, 1, lanes_in_flight(cus, Knob::IterLanes), kIterFloor);
     KmerDev kmv;
     const KmerDev *km = kmer_device(res, n, &kmv) ? &kmv : nullptr;
     hipError_t e = launch_find_iter_multi(b, (int)n, fs.data(), rs.data(), chunk, os.data(), st, cus, sps.data(), km);
@@ -729,26 +684,25 @@ int rure_amd_replace_all_chain(rure *const *res, const uint8_t *const *reps, con
         at += img[x].size();
       }
       memcpy(blob.data() + 1024 + kHMapPoolMax, dl.data(), dl.size() * 4);
-      uint8_t *db = nullptr;
-      hipError_t e = scratch_malloc((void **)&db, blob.size(), st);
-      if (e == hipSuccess) e = hipMemcpyAsync(db, blob.data(), blob.size(), hipMemcpyHostToDevice, st);
+      Scratch<uint8_t> db;
+      hipError_t e = db.alloc(blob.size(), st);
+      if (e == hipSuccess) e = hipMemcpyAsync(db.get(), blob.data(), blob.size(), hipMemcpyHostToDevice, st);
       uint8_t *out = (n & 1) ? out0 : out1;
       if (e == hipSuccess)
-        e = launch_replace_hmap(haystack, length, (int)n, db, (uint32_t)pool, nact, out, capacity, lengths, st,
+        e = launch_replace_hmap(haystack, length, (int)n, db.get(), (uint32_t)pool, nact, out, capacity, lengths, st,
                                 cus);
-      if (db) { const hipError_t e2 = scratch_free(db, st); if (e == hipSuccess) e = e2; }
       if (e == hipSuccess) note_fwd_path(RURE_AMD_PATH_REPLACE_HMAP);
       if (e != hipErrorNotSupported) return e == hipSuccess ? RURE_AMD_OK : RURE_AMD_ERR_HIP;
     }
   }
-  uint8_t *dt = nullptr;
-  hipError_t e = scratch_malloc((void **)&dt, host.size(), st);
-  if (e == hipSuccess) e = hipMemcpyAsync(dt, host.data(), host.size(), hipMemcpyHostToDevice, st);
+  Scratch<uint8_t> dt;
+  hipError_t e = dt.alloc(host.size(), st);
+  if (e == hipSuccess) e = hipMemcpyAsync(dt.get(), host.data(), host.size(), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) {
     std::vector<const uint8_t *> cls(n), rep(n);
     for (size_t i = 0; i < n; ++i) {
-      cls[i] = dt + i * 320;
-      rep[i] = dt + i * 320 + 256;
+      cls[i] = dt.get() + i * 320;
+      rep[i] = dt.get() + i * 320 + 256;
     }
     // the bytes of each replacement in the next step's class
     std::vector<uint32_t> nrep(n, 0);
@@ -758,7 +712,6 @@ int rure_amd_replace_all_chain(rure *const *res, const uint8_t *const *reps, con
                                    (const uint32_t(*)[2])sw.data(), nrep.data(), out0, out1, capacity, lengths, st,
                                    cus);
   }
-  if (dt) { const hipError_t e2 = scratch_free(dt, st); if (e == hipSuccess) e = e2; }
   if (e == hipErrorNotSupported) return RURE_AMD_ERR_ARG;
   if (e == hipSuccess) note_fwd_path(RURE_AMD_PATH_REPLACE_CLASS);
   return e == hipSuccess ? RURE_AMD_OK : RURE_AMD_ERR_HIP;
@@ -781,10 +734,10 @@ int rure_amd_replace_batch(rure *re, const rure_amd_batch *batch, const uint8_t 
   // one haystack: no match list (launch_replace_class); no synchronisation
   if (re->cls_one_ok && b.count == 1 && !b.offs && b.start == 0 && lim == ~0ull && rep_len >= 1 && rep_len <= 64 &&
       knob(Knob::ReplaceGeneric) != 1) {
-    uint8_t *dt = nullptr;
-    hipError_t e = scratch_malloc((void **)&dt, 256 + 64, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dt, re->cls_one, 256, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dt + 256, rep, rep_len, hipMemcpyHostToDevice, st);
+    Scratch<uint8_t> dt;
+    hipError_t e = dt.alloc(256 + 64, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dt.get(), re->cls_one, 256, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dt.get() + 256, rep, rep_len, hipMemcpyHostToDevice, st);
     // (a class of one or two bytes: SWAR compares instead of the table; byte
     // 0 can not be a repeated compare value, it would read as "no class")
     uint32_t sw[2] = {0, 0}, nb = 0;
@@ -793,36 +746,33 @@ int rure_amd_replace_batch(rure *re, const rure_amd_batch *batch, const uint8_t 
     if (re->cls_one[0] || nb > 2) sw[0] = sw[1] = 0;
     else if (nb == 1) sw[1] = sw[0];
     if (e == hipSuccess)
-      e = launch_replace_class(b.hay, b.length, dt, dt + 256, (uint32_t)rep_len, out, out_capacity, out_offsets, total,
-                               st, t->cus, sw[0], sw[1]);
-    if (dt) { const hipError_t e2 = scratch_free(dt, st); if (e == hipSuccess) e = e2; }
+      e = launch_replace_class(b.hay, b.length, dt.get(), dt.get() + 256, (uint32_t)rep_len, out, out_capacity,
+                               out_offsets, total, st, t->cus, sw[0], sw[1]);
     if (e != hipErrorNotSupported) {
       if (e == hipSuccess) note_fwd_path(RURE_AMD_PATH_REPLACE_CLASS);
       return e == hipSuccess ? RURE_AMD_OK : RURE_AMD_ERR_HIP;
     }
   }
   IterBufs ib;
-  int64_t *shift = nullptr;
-  uint64_t *olen = nullptr;
-  uint8_t *drep = nullptr;
+  Scratch<int64_t> shift;
+  Scratch<uint64_t> olen;
+  Scratch<uint8_t> drep;
   hipError_t e = iter_to_device(re, t, b, st, &ib, &err);
-  if (e == hipSuccess) e = scratch_malloc((void **)&shift, (ib.nm + 1) * 8, st);
-  if (e == hipSuccess) e = scratch_malloc((void **)&olen, (b.count + 1) * 8, st);
-  if (e == hipSuccess) e = scratch_malloc((void **)&drep, std::max<size_t>(rep_len, 1), st);
-  if (e == hipSuccess && rep_len) e = hipMemcpyAsync(drep, rep, rep_len, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemsetAsync(olen + b.count, 0, 8, st);
+  if (e == hipSuccess) e = shift.alloc((ib.nm + 1) * 8, st);
+  if (e == hipSuccess) e = olen.alloc((b.count + 1) * 8, st);
+  if (e == hipSuccess) e = drep.alloc(std::max<size_t>(rep_len, 1), st);
+  if (e == hipSuccess && rep_len) e = hipMemcpyAsync(drep.get(), rep, rep_len, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemsetAsync(olen.get() + b.count, 0, 8, st);
+  const uint64_t *counts = ib.counts.get(), *moff = ib.moff.get(), *m = ib.m.get();
   if (e == hipSuccess)
-    e = launch_replace_plan(b, ib.counts, ib.moff, ib.m, lim, rep_len, shift, olen, st, t->cus, ib.nm);
-  if (e == hipSuccess) e = exclusive_scan_u64(olen, out_offsets, b.count + 1, st);
+    e = launch_replace_plan(b, counts, moff, m, lim, rep_len, shift.get(), olen.get(), st, t->cus, ib.nm);
+  if (e == hipSuccess) e = exclusive_scan_u64(olen.get(), out_offsets, b.count + 1, st);
   if (e == hipSuccess) e = hipMemcpyAsync(total, out_offsets + b.count, 8, hipMemcpyDeviceToDevice, st);
   if (e == hipSuccess && out_capacity) {
     const uint64_t hint = b.offs ? out_capacity : std::min<uint64_t>(out_capacity, b.count * b.length + ib.nm * rep_len);
-    e = launch_replace_copy(b, out_offsets, ib.counts, ib.moff, ib.m, shift, lim, drep, rep_len, out, out_capacity,
+    e = launch_replace_copy(b, out_offsets, counts, moff, m, shift.get(), lim, drep.get(), rep_len, out, out_capacity,
                             hint, st, t->cus, ib.nm);
   }
-  if (shift) (void)scratch_free(shift, st);
-  if (olen) (void)scratch_free(olen, st);
-  if (drep) (void)scratch_free(drep, st);
   return e == hipSuccess ? RURE_AMD_OK : RURE_AMD_ERR_HIP;
 }
 
@@ -841,28 +791,27 @@ int rure_amd_captures_iter_batch(rure *re, const rure_amd_batch *batch, uint64_t
   const uint32_t ns = capture_slots(re);
   if (!re->nfa_ok && (ns > 2 || !t->has_dfa)) return RURE_AMD_ERR_DFA;
   IterBufs ib;
-  uint64_t *tmp = nullptr;
+  Scratch<uint64_t> tmp;
   hipError_t e = iter_to_device(re, t, b, st, &ib, &err);
   if (e == hipSuccess) e = hipMemsetAsync(diverged, 0, b.count, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(counts, ib.counts, b.count * 8, hipMemcpyDeviceToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(total, ib.total, 8, hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(counts, ib.counts.get(), b.count * 8, hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(total, ib.total.get(), 8, hipMemcpyDeviceToDevice, st);
   const uint64_t nrows = std::min<uint64_t>(ib.nm, capacity);
   if (e == hipSuccess && ns <= 2) {
     // one group: the reference's captures are its plain find (exec.rs:533-541)
-    if (nrows) e = hipMemcpyAsync(slots, ib.m, nrows * 16, hipMemcpyDeviceToDevice, st);
+    if (nrows) e = hipMemcpyAsync(slots, ib.m.get(), nrows * 16, hipMemcpyDeviceToDevice, st);
   } else if (e == hipSuccess && ib.nm) {
     // every match is run (a short `slots` must not hide a divergence): into
     // the caller's rows when they hold all of them, else into scratch
     uint64_t *rows = (uint64_t *)slots;
     if (ib.nm > capacity) {
-      e = scratch_malloc((void **)&tmp, ib.nm * ns * 8, st);
-      rows = tmp;
+      e = tmp.alloc(ib.nm * ns * 8, st);
+      rows = tmp.get();
     }
     if (e == hipSuccess) e = run_captures_iter(b, *t, ib, ~0ull, rows, ns, diverged, st);
     if (e == hipSuccess && tmp && nrows)
-      e = hipMemcpyAsync(slots, tmp, nrows * ns * 8, hipMemcpyDeviceToDevice, st);
+      e = hipMemcpyAsync(slots, tmp.get(), nrows * ns * 8, hipMemcpyDeviceToDevice, st);
   }
-  if (tmp) (void)scratch_free(tmp, st);
   if (e == hipSuccess) note_fwd_path(RURE_AMD_PATH_CAPTURES_ITER);
   return e == hipSuccess ? RURE_AMD_OK : RURE_AMD_ERR_HIP;
 }
@@ -910,37 +859,35 @@ int rure_amd_replace_expand_batch(rure *re, const rure_amd_batch *batch, const u
     hp[3 * i + 2] = tp.pieces[i].b;
   }
   IterBufs ib;
-  uint64_t *rows = nullptr, *seg = nullptr, *S = nullptr, *olen = nullptr, *units = nullptr, *uoff = nullptr;
-  uint32_t *dp = nullptr;
-  uint8_t *dl = nullptr;
+  Scratch<uint64_t> rows, seg, S, olen, units, uoff;
+  Scratch<uint32_t> dp;
+  Scratch<uint8_t> dl;
   hipError_t e = iter_to_device(re, t, b, st, &ib, &err);
   if (e == hipSuccess) e = hipMemsetAsync(diverged, 0, b.count, st);
-  if (e == hipSuccess && need_caps && ib.nm) e = scratch_malloc((void **)&rows, ib.nm * ns * 8, st);
-  if (e == hipSuccess) e = scratch_malloc((void **)&seg, (ib.nm + 1) * 8, st);
-  if (e == hipSuccess) e = scratch_malloc((void **)&S, (ib.nm + 1) * 8, st);
-  if (e == hipSuccess) e = scratch_malloc((void **)&olen, (b.count + 1) * 8, st);
-  if (e == hipSuccess && b.offs) e = scratch_malloc((void **)&units, (b.count + 1) * 8, st);
-  if (e == hipSuccess && b.offs) e = scratch_malloc((void **)&uoff, (b.count + 1) * 8, st);
-  if (e == hipSuccess) e = scratch_malloc((void **)&dp, hp.size() * 4, st);
-  if (e == hipSuccess) e = scratch_malloc((void **)&dl, std::max<size_t>(tp.lits.size(), 1), st);
-  if (e == hipSuccess) e = hipMemcpyAsync(dp, hp.data(), hp.size() * 4, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && need_caps && ib.nm) e = rows.alloc(ib.nm * ns * 8, st);
+  if (e == hipSuccess) e = seg.alloc((ib.nm + 1) * 8, st);
+  if (e == hipSuccess) e = S.alloc((ib.nm + 1) * 8, st);
+  if (e == hipSuccess) e = olen.alloc((b.count + 1) * 8, st);
+  if (e == hipSuccess && b.offs) e = units.alloc((b.count + 1) * 8, st);
+  if (e == hipSuccess && b.offs) e = uoff.alloc((b.count + 1) * 8, st);
+  if (e == hipSuccess) e = dp.alloc(hp.size() * 4, st);
+  if (e == hipSuccess) e = dl.alloc(std::max<size_t>(tp.lits.size(), 1), st);
+  if (e == hipSuccess) e = hipMemcpyAsync(dp.get(), hp.data(), hp.size() * 4, hipMemcpyHostToDevice, st);
   if (e == hipSuccess && !tp.lits.empty())
-    e = hipMemcpyAsync(dl, tp.lits.data(), tp.lits.size(), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && need_caps) e = run_captures_iter(b, *t, ib, lim, rows, ns, diverged, st);
-  const uint64_t *r = need_caps ? rows : ib.m;
+    e = hipMemcpyAsync(dl.get(), tp.lits.data(), tp.lits.size(), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && need_caps) e = run_captures_iter(b, *t, ib, lim, rows.get(), ns, diverged, st);
+  const uint64_t *counts = ib.counts.get(), *moff = ib.moff.get(), *m = ib.m.get();
+  const uint64_t *r = need_caps ? rows.get() : m;
   const uint32_t rns = need_caps ? ns : 2;
-  const ExpandTpl dt{dp, (uint32_t)tp.pieces.size(), dl, tp.lits.size()};
+  const ExpandTpl dt{dp.get(), (uint32_t)tp.pieces.size(), dl.get(), tp.lits.size()};
   if (e == hipSuccess)
-    e = launch_expand_plan(b, ib.counts, ib.moff, ib.m, ib.nm, lim, r, rns, dt, seg, S, olen, out_offsets, st);
+    e = launch_expand_plan(b, counts, moff, m, ib.nm, lim, r, rns, dt, seg.get(), S.get(), olen.get(), out_offsets, st);
   if (e == hipSuccess) e = hipMemcpyAsync(total, out_offsets + b.count, 8, hipMemcpyDeviceToDevice, st);
   if (e == hipSuccess && out_capacity)
-    e = launch_expand_write(b, ib.counts, ib.moff, ib.m, ib.nm, lim, r, rns, dt, S, out_offsets, units, uoff, out,
-                            out_capacity, st, t->cus);
+    e = launch_expand_write(b, counts, moff, m, ib.nm, lim, r, rns, dt, S.get(), out_offsets, units.get(), uoff.get(),
+                            out, out_capacity, st, t->cus);
   // the host copies above read hp / tp.lits, which die with this call
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  for (void *p : {(void *)rows, (void *)seg, (void *)S, (void *)olen, (void *)units, (void *)uoff, (void *)dp,
-                  (void *)dl})
-    if (p) (void)scratch_free(p, st);
   if (e == hipSuccess) note_fwd_path(RURE_AMD_PATH_REPLACE_EXPAND);
   return e == hipSuccess ? RURE_AMD_OK : RURE_AMD_ERR_HIP;
 }
@@ -957,18 +904,16 @@ int rure_amd_split_batch(rure *re, const rure_amd_batch *batch, size_t limit, ui
   if (!t) return err.rfind("HIP", 0) == 0 ? RURE_AMD_ERR_HIP : RURE_AMD_ERR_DFA;
   if (!t->has_dfa && !re->nfa_ok) return RURE_AMD_ERR_DFA;
   IterBufs ib;
-  uint64_t *fields = nullptr, *foff = nullptr;
+  Scratch<uint64_t> fields, foff;
   hipError_t e = iter_to_device(re, t, b, st, &ib, &err);
-  if (e == hipSuccess) e = scratch_malloc((void **)&fields, (b.count + 1) * 8, st);
-  if (e == hipSuccess) e = scratch_malloc((void **)&foff, (b.count + 1) * 8, st);
-  if (e == hipSuccess) e = hipMemsetAsync(fields + b.count, 0, 8, st);
+  if (e == hipSuccess) e = fields.alloc((b.count + 1) * 8, st);
+  if (e == hipSuccess) e = foff.alloc((b.count + 1) * 8, st);
+  if (e == hipSuccess) e = hipMemsetAsync(fields.get() + b.count, 0, 8, st);
   if (e == hipSuccess)
-    e = launch_split(b, ib.counts, ib.moff, ib.m, (uint64_t)limit, fields, foff, (uint64_t *)pieces, capacity, ib.nm,
-                     st, t->cus);
-  if (e == hipSuccess) e = hipMemcpyAsync(counts, fields, b.count * 8, hipMemcpyDeviceToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(total, foff + b.count, 8, hipMemcpyDeviceToDevice, st);
-  if (fields) (void)scratch_free(fields, st);
-  if (foff) (void)scratch_free(foff, st);
+    e = launch_split(b, ib.counts.get(), ib.moff.get(), ib.m.get(), (uint64_t)limit, fields.get(), foff.get(),
+                     (uint64_t *)pieces, capacity, ib.nm, st, t->cus);
+  if (e == hipSuccess) e = hipMemcpyAsync(counts, fields.get(), b.count * 8, hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(total, foff.get() + b.count, 8, hipMemcpyDeviceToDevice, st);
   return e == hipSuccess ? RURE_AMD_OK : RURE_AMD_ERR_HIP;
 }
 

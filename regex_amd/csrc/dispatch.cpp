@@ -111,7 +111,7 @@ int grid_for(size_t count, uint32_t lds_bytes, int cus) {
 }
 
 
-int pike_grid(size_t count, bool fallback, const NfaDev &n, int cus) {
+static int pike_grid(size_t count, bool fallback, const NfaDev &n, int cus) {
   size_t units = fallback ? (count + 63) / 64 : count;
   size_t wb = nfa_wave_bytes(n.nleaves);
   size_t per_cu = wb <= kNfaLdsMax ? std::max<size_t>(1, std::min<size_t>(32, (160u * 1024u) / wb)) : 4;
@@ -120,38 +120,37 @@ int pike_grid(size_t count, bool fallback, const NfaDev &n, int cus) {
 }
 
 // Pike VM pass: all haystacks (no DFA) or only those the DFA quit on.
-hipError_t run_pike(int mode, bool fallback, const BatchDev &b, const DevTables &t, void *out, hipStream_t st) {
+static hipError_t run_pike(int mode, bool fallback, const BatchDev &b, const DevTables &t, void *out, hipStream_t st) {
   if (!fallback) note_fwd_path(RURE_AMD_PATH_PIKE_ONLY);
   int grid = pike_grid(b.count, fallback, t.n, t.cus);
   size_t wb = nfa_wave_bytes(t.n.nleaves);
   if (wb <= kNfaLdsMax) return launch_pike(mode, fallback, b, t.n, out, nullptr, st, grid);
-  void *scratch = nullptr;
-  hipError_t e = scratch_malloc(&scratch, wb * (size_t)grid, st);
+  Scratch<> scratch;
+  const hipError_t e = scratch.alloc(wb * (size_t)grid, st);
   if (e != hipSuccess) return e;
-  e = launch_pike(mode, fallback, b, t.n, out, scratch, st, grid);
-  hipError_t e2 = scratch_free(scratch, st);
-  return e != hipSuccess ? e : e2;
+  return launch_pike(mode, fallback, b, t.n, out, scratch.get(), st, grid);
 }
 
 
 // The engine dispatch of exec.rs:473-514 / 382-420 for a batch: DFA, and the
 // Pike VM where the DFA quits (or instead of it when it does not fit).
-// Chunk sizes are an odd number of 128-byte lines: lanes that scan chunks in
-// lockstep then read addresses with different low bits, instead of hammering
-// the few HBM channels a power-of-two chunk would map them all to.
-uint64_t odd_lines(uint64_t bytes) {
-  uint64_t lines = (bytes + 127) / 128;
-  if ((lines & 1) == 0) ++lines;
-  return lines * 128;
+// The unit sizes of its chunked paths are host/chunk_plan.hpp's rule.
+
+// The lanes in flight: kLanesPerCu per CU, or what a tuning knob
+// (RURE_AMD_LONG_LANES, RURE_AMD_ITER_LANES; per CU) says.
+uint64_t lanes_in_flight(int cus, Knob k) {
+  uint64_t per_cu = kLanesPerCu;
+  if (knob(k) > 0) per_cu = std::max<uint64_t>(64, knob(k));
+  return (uint64_t)cus * per_cu;
 }
 
 // Few long haystacks: one lane per haystack would leave the chip idle, so the
 // search is split into chunks (launch_long_scan).  Needs a DFA that cannot
 // quit (the Pike VM fallback is per haystack).
-bool long_batch(int mode, const BatchDev &b, const DevTables &t, uint64_t *chunk) {
+static bool long_batch(int mode, const BatchDev &b, const DevTables &t, uint64_t *chunk) {
   if (b.offs || !t.has_dfa || t.quit_possible || b.count == 0) return false;
   const uint64_t span = b.length > b.start ? b.length - b.start : 0;
-  if (span < (256u << 10) || b.count >= (uint64_t)t.cus * 128) {
+  if (span < kLongSpan || b.count >= (uint64_t)t.cus * 128) {
     // Small batches of medium haystacks (C1: 1024 x 1 KiB): one lane per
     // haystack runs count / 256 workgroups on a 256-CU chip, each lane a
     // dependent chain over its whole haystack; units of >= 128 B spread the
@@ -165,20 +164,12 @@ bool long_batch(int mode, const BatchDev &b, const DevTables &t, uint64_t *chunk
     if (knob(Knob::Split) == 0 || mode != MODE_ISMATCH || t.anchored_rev || span < 512 || b.count < 64 ||
         b.count > (uint64_t)t.cus * 16)
       return false;
-    const uint64_t per_h = ((uint64_t)t.cus * 64 + b.count - 1) / b.count;
-    const uint64_t c = odd_lines(std::max<uint64_t>(128, (span + per_h - 1) / per_h));
-    if (c >= span) return false;
+    const uint64_t c = split_unit_bytes(span, b.count, (uint64_t)t.cus);
+    if (!c) return false;
     *chunk = c;
     return true;
   }
-  // 16 waves per CU: per-lane streams need latency hiding (RURE_AMD_LONG_LANES
-  // per CU overrides, tuning)
-  uint64_t per_cu = 1024;
-  if (knob(Knob::LongLanes) > 0) per_cu = std::max<uint64_t>(64, knob(Knob::LongLanes));
-  const uint64_t target = (uint64_t)t.cus * per_cu;
-  const uint64_t per_h = (target + b.count - 1) / b.count;
-  uint64_t c = std::max<uint64_t>(16u << 10, (span + per_h - 1) / per_h);
-  *chunk = odd_lines(c);
+  *chunk = unit_bytes(span, b.count, lanes_in_flight(t.cus, Knob::LongLanes), kLongFloor);
   return true;
 }
 
@@ -187,8 +178,8 @@ bool long_batch(int mode, const BatchDev &b, const DevTables &t, uint64_t *chunk
 // regexes the reverse DFA from the end of each haystack.  Long haystacks
 // searched from their start take the chunked forward scan for either (the
 // two answer alike at start 0: only the look-behind at `start` differs).
-hipError_t run_dfa_step(int mode, const BatchDev &b, const DevTables &t, void *out, hipStream_t st, int dfa_grid,
-                        const FwdDfaDev *iter) {
+static hipError_t run_dfa_step(int mode, const BatchDev &b, const DevTables &t, void *out, hipStream_t st,
+                               int dfa_grid, const FwdDfaDev *iter) {
   uint64_t chunk = 0;
   const bool long_fwd = iter && long_batch(mode, b, t, &chunk);
   if (t.anchored_rev && !(long_fwd && b.start == 0)) return launch_dfa_anchored_rev(mode, b, t.r, out, st, dfa_grid);
@@ -205,27 +196,34 @@ bool lane_search_ok(const DevTables &t) { return t.mt_lane && (t.m.mt != MT_DFA_
 // cut into units (launch_suffix_long) instead of one lane per haystack; the
 // haystacks where the reference falls back to the forward DFA (None) then
 // take the chunked forward scan.  RURE_AMD_SUFFIX_LONG=0 keeps the lanes.
-bool suffix_long_ok(const BatchDev &b, const DevTables &t, uint64_t *chunk) {
+// The unit of the two chunked DfaSuffix paths (the scan below and the
+// iteration of run_find_iter): the long scan's rule, one line's floor where a
+// test forces the path at any length.  Kept from before: a fixed kLanesPerCu,
+// the lanes knobs do not reach these paths.
+static uint64_t suffix_unit_bytes(uint64_t span, uint64_t count, int cus, bool forced) {
+  return unit_bytes(span, count, (uint64_t)cus * kLanesPerCu, forced ? kLineFloor : kLongFloor);
+}
+
+static bool suffix_long_ok(const BatchDev &b, const DevTables &t, uint64_t *chunk) {
   if (t.m.mt != MT_DFA_SUFFIX || !t.lcs_free || !t.has_dfa || t.quit_possible || b.offs || b.count == 0 || !t.owner)
     return false;
   if (knob(Knob::SuffixLong) == 0) return false;
   const uint64_t span = b.length > b.start ? b.length - b.start : 0;
-  if (b.count >= (uint64_t)t.cus * 16 || (span < (256u << 10) && knob(Knob::SuffixLong) != 2)) return false;
-  const uint64_t target = (uint64_t)t.cus * 1024;
-  const uint64_t per_h = (target + b.count - 1) / b.count;
-  *chunk = odd_lines(std::max<uint64_t>(knob(Knob::SuffixLong) == 2 ? 128 : 16u << 10, (span + per_h - 1) / per_h));
+  const bool forced = knob(Knob::SuffixLong) == 2;
+  if (b.count >= (uint64_t)t.cus * 16 || (span < kLongSpan && !forced)) return false;
+  *chunk = suffix_unit_bytes(span, b.count, t.cus, forced);
   return true;
 }
 
-hipError_t run_suffix_long(int mode, const BatchDev &b, const DevTables &t, uint64_t chunk, void *out,
-                           hipStream_t st) {
-  uint8_t *status = nullptr;
-  hipError_t e = scratch_malloc((void **)&status, b.count, st);
-  if (e == hipSuccess) e = launch_suffix_long(mode, b, t.m, t.f, t.r, chunk, out, status, st, t.cus);
+static hipError_t run_suffix_long(int mode, const BatchDev &b, const DevTables &t, uint64_t chunk, void *out,
+                                  hipStream_t st) {
+  Scratch<uint8_t> status;
+  hipError_t e = status.alloc(b.count, st);
+  if (e == hipSuccess) e = launch_suffix_long(mode, b, t.m, t.f, t.r, chunk, out, status.get(), st, t.cus);
   std::vector<uint8_t> hs(b.count);
-  if (e == hipSuccess) e = hipMemcpyAsync(hs.data(), status, b.count, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(hs.data(), status.get(), b.count, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (status) { hipError_t e2 = scratch_free(status, st); if (e == hipSuccess) e = e2; }
+  status.reset();  // before the forward scan's scratch
   if (e != hipSuccess) return e;
   size_t nf = 0;
   for (uint8_t x : hs) nf += x == 3;
@@ -238,37 +236,43 @@ hipError_t run_suffix_long(int mode, const BatchDev &b, const DevTables &t, uint
   if (!long_batch(mode, b, t, &fchunk)) fchunk = chunk;
   const size_t rec = mode == MODE_FIND ? 16 : mode == MODE_SHORTEST ? 8 : 1;
   if (nf == b.count) return launch_long_scan(mode, b, *iter, t.r, fchunk, out, st, t.cus);
-  void *tmp = nullptr;
-  e = scratch_malloc(&tmp, b.count * rec, st);
-  if (e == hipSuccess) e = launch_long_scan(mode, b, *iter, t.r, fchunk, tmp, st, t.cus);
+  Scratch<uint8_t> tmp;
+  e = tmp.alloc(b.count * rec, st);
+  if (e == hipSuccess) e = launch_long_scan(mode, b, *iter, t.r, fchunk, tmp.get(), st, t.cus);
   for (size_t h = 0; e == hipSuccess && h < b.count; ++h)
-    if (hs[h] == 3)
-      e = hipMemcpyAsync((uint8_t *)out + h * rec, (uint8_t *)tmp + h * rec, rec, hipMemcpyDeviceToDevice, st);
-  if (tmp) { hipError_t e2 = scratch_free(tmp, st); if (e == hipSuccess) e = e2; }
+    if (hs[h] == 3) e = hipMemcpyAsync((uint8_t *)out + h * rec, tmp.get() + h * rec, rec, hipMemcpyDeviceToDevice, st);
   return e;
 }
 
-hipError_t run_lane_search(int mode, const BatchDev &b, const DevTables &t, void *out, hipStream_t st) {
+// A DFA step that can quit, then the Pike VM over the haystacks it quit on:
+// the DFA kernels flag a quit in b.quit_flag (`step` gets the batch with the
+// flag), and the Pike VM fallback returns at once without one.
+template <class Step>
+static hipError_t with_quit_fallback(int mode, const BatchDev &b, const DevTables &t, void *out, hipStream_t st,
+                                     Step step) {
+  Scratch<uint32_t> flag;
+  hipError_t e = flag.alloc(4, st);
+  BatchDev bq = b;
+  bq.quit_flag = flag.get();
+  if (e == hipSuccess) e = hipMemsetAsync(bq.quit_flag, 0, 4, st);
+  if (e == hipSuccess) e = step(bq);
+  if (e == hipSuccess) e = run_pike(mode, true, bq, t, out, st);
+  return e;
+}
+
+static hipError_t run_lane_search(int mode, const BatchDev &b, const DevTables &t, void *out, hipStream_t st) {
   uint64_t chunk = 0;
   if (suffix_long_ok(b, t, &chunk)) return run_suffix_long(mode, b, t, chunk, out, st);
-  if (!t.quit_possible || t.m.mt != MT_DFA_SUFFIX) return launch_lane_search(mode, b, t.m, t.f, t.r, out, st, t.cus);
-  BatchDev bq = b;  // quit flag: see run_regex
-  hipError_t e = scratch_malloc((void **)&bq.quit_flag, 4, st);
-  if (e == hipSuccess) e = hipMemsetAsync(bq.quit_flag, 0, 4, st);
-  if (e == hipSuccess) e = launch_lane_search(mode, bq, t.m, t.f, t.r, out, st, t.cus);
-  if (e == hipSuccess) e = run_pike(mode, true, bq, t, out, st);
-  if (bq.quit_flag) {
-    hipError_t e2 = scratch_free(bq.quit_flag, st);
-    if (e == hipSuccess) e = e2;
-  }
-  return e;
+  const auto step = [&](const BatchDev &bq) { return launch_lane_search(mode, bq, t.m, t.f, t.r, out, st, t.cus); };
+  if (!t.quit_possible || t.m.mt != MT_DFA_SUFFIX) return step(b);
+  return with_quit_fallback(mode, b, t, out, st, step);
 }
 
 // The big-DFA kernel runs one lane per haystack: for batches that fill the
 // device (a handful of long haystacks stay on the Pike VM, which spreads one
 // haystack over a wave).  RURE_AMD_BIG=2 forces it (tests), =0 keeps the
 // Pike VM (A/B; read per call).
-bool big_batch(const BatchDev &b, const DevTables &t) {
+static bool big_batch(const BatchDev &b, const DevTables &t) {
   if (knob(Knob::Big) == 2) return true;
   if (knob(Knob::Big) == 0) return false;
   return b.count >= (uint64_t)t.cus * 64;
@@ -282,7 +286,7 @@ bool big_batch(const BatchDev &b, const DevTables &t) {
 // the cache thrashes (dfa.rs:1282-1293) and runs the Pike VM; here a spent
 // memory budget or kLazyRounds rounds do the same for the batch.
 constexpr int kLazyRounds = 256;
-hipError_t run_lazy(int mode, const BatchDev &b, const DevTables &tc, void *out, hipStream_t st) {
+static hipError_t run_lazy(int mode, const BatchDev &b, const DevTables &tc, void *out, hipStream_t st) {
   DevTables &t = const_cast<DevTables &>(tc);
   rure *re = t.owner;
   std::lock_guard<std::mutex> g(re->mu);
@@ -291,12 +295,12 @@ hipError_t run_lazy(int mode, const BatchDev &b, const DevTables &tc, void *out,
   if (knob(Knob::LazyRows) > 0) ahead = (size_t)knob(Knob::LazyRows);
   bool ok = L.nbuilt() > 0 || L.expand(ahead);
   hipError_t e = hipSuccess;
-  LazyPark *pk[2] = {nullptr, nullptr};
-  unsigned long long *cnt = nullptr;
+  Scratch<LazyPark> pk[2];
+  Scratch<unsigned long long> cnt;
   const size_t pbytes = std::max<uint64_t>(b.count, 1) * sizeof(LazyPark);
-  if ((e = scratch_malloc((void **)&pk[0], pbytes, st)) != hipSuccess) return e;
-  if ((e = scratch_malloc((void **)&pk[1], pbytes, st)) != hipSuccess) return e;
-  if ((e = scratch_malloc((void **)&cnt, 16, st)) != hipSuccess) return e;
+  if ((e = pk[0].alloc(pbytes, st)) != hipSuccess) return e;
+  if ((e = pk[1].alloc(pbytes, st)) != hipSuccess) return e;
+  if ((e = cnt.alloc(16, st)) != hipSuccess) return e;
   const LazyPark *in = nullptr;
   uint64_t nin = 0;
   std::vector<LazyPark> host;
@@ -325,11 +329,11 @@ hipError_t run_lazy(int mode, const BatchDev &b, const DevTables &tc, void *out,
     f.trans = (const uint32_t *)(base + o_trans);
     f.ncol = L.ncol;
     f.hot = std::min<uint32_t>((uint32_t)ns, lazy_dfa_hot_rows(L.ncol));
-    LazyPark *po = pk[round & 1];
-    if ((e = hipMemsetAsync(cnt, 0, 8, st)) != hipSuccess) break;
-    if ((e = launch_lazy_dfa(mode, b, f, t.lr, in, nin, po, cnt, out, st, t.cus)) != hipSuccess) break;
+    LazyPark *po = pk[round & 1].get();
+    if ((e = hipMemsetAsync(cnt.get(), 0, 8, st)) != hipSuccess) break;
+    if ((e = launch_lazy_dfa(mode, b, f, t.lr, in, nin, po, cnt.get(), out, st, t.cus)) != hipSuccess) break;
     unsigned long long n = 0;
-    if ((e = hipMemcpyAsync(&n, cnt, 8, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
+    if ((e = hipMemcpyAsync(&n, cnt.get(), 8, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
     if ((e = hipStreamSynchronize(st)) != hipSuccess) break;
     if (n == 0) break;
     if (round + 1 >= kLazyRounds) { ok = false; break; }
@@ -337,21 +341,18 @@ hipError_t run_lazy(int mode, const BatchDev &b, const DevTables &tc, void *out,
     if ((e = hipMemcpyAsync(host.data(), po, n * sizeof(LazyPark), hipMemcpyDeviceToHost, st)) != hipSuccess ||
         (e = hipStreamSynchronize(st)) != hipSuccess)
       break;
-    size_t built0 = L.nbuilt();
     for (const LazyPark &x : host)
       if (!(ok = L.build_row(x.s))) break;
     // (a fixed number ahead: doubling the rows built ahead each round built
     // states in discovery order the text never visits, seconds of host work
     // for (?:a|b)*a(?:a|b){20})
-    (void)built0;
     if (ok) ok = L.expand(ahead);
     in = po;
     nin = n;
   }
-  for (int k = 0; k < 2; ++k) { hipError_t e2 = scratch_free(pk[k], st); if (e == hipSuccess) e = e2; }
-  { hipError_t e2 = scratch_free(cnt, st); if (e == hipSuccess) e = e2; }
-  if (e == hipSuccess && !ok) e = run_pike(mode, false, b, t, out, st);  // the whole batch again
-  return e;
+  if (e != hipSuccess || ok) return e;
+  pk[0].reset(), pk[1].reset(), cnt.reset();  // before the Pike VM's scratch
+  return run_pike(mode, false, b, t, out, st);  // the whole batch again
 }
 
 // The on-demand DFA where the eager automata did not materialise (or
@@ -367,7 +368,7 @@ static bool lazy_batch(const BatchDev &b, const DevTables &t) {
 // shortest_match: one lane per haystack would walk a long document alone
 // (64 MiB: seconds), and the host knows no length without reading the offsets
 // back, which these calls never do (they only enqueue).  So the lane kernel
-// defers: a haystack whose span reaches 256 KiB (long_batch's threshold) goes
+// defers: a haystack whose span reaches kLongSpan (long_batch's threshold) goes
 // on a device list and gets "no match"; the chunk, the units and the chunked
 // scan of the listed haystacks follow on the device (launch_long_ragged),
 // empty launches when nothing was listed.  For a forward DFA that cannot
@@ -375,7 +376,7 @@ static bool lazy_batch(const BatchDev &b, const DevTables &t) {
 // has none: its lanes die where the text stops matching).  Knobs long_ragged:
 // 0 never, 2 every haystack longer than one chunk; long_chunk: the chunk
 // floor (tests: cuts everywhere); long_list: the list's capacity.
-const FwdDfaDev *ragged_long_iter(rure *re, const BatchDev &b, const DevTables &t) {
+static const FwdDfaDev *ragged_long_iter(rure *re, const BatchDev &b, const DevTables &t) {
   if (!b.offs || !b.count || !t.has_dfa || t.quit_possible || t.anchored_rev || lane_search_ok(t)) return nullptr;
   if (knob(Knob::LongRagged) == 0) return nullptr;
   std::string err;
@@ -400,15 +401,13 @@ static uint64_t device_mem_cached() {
 // scratch holds the list and the units' results for the most there can be:
 // no buffer of the device holds more than memory / threshold haystacks of
 // that length, and units <= listed + lanes (long_scan.hip).
-hipError_t run_ragged_long(int mode, const BatchDev &b, const DevTables &t, const FwdDfaDev &iter, bool lit, void *out,
-                           hipStream_t st, int dfa_grid) {
-  uint64_t per_cu = 1024;  // long_batch's lanes in flight
-  if (knob(Knob::LongLanes) > 0) per_cu = std::max<uint64_t>(64, knob(Knob::LongLanes));
-  const uint64_t lanes = (uint64_t)t.cus * per_cu;
+static hipError_t run_ragged_long(int mode, const BatchDev &b, const DevTables &t, const FwdDfaDev &iter, bool lit,
+                                  void *out, hipStream_t st, int dfa_grid) {
+  const uint64_t lanes = lanes_in_flight(t.cus, Knob::LongLanes);  // long_batch's
   const bool any = knob(Knob::LongRagged) == 2;
   const long long kc = knob(Knob::LongChunk);
-  const uint64_t floor = kc > 0 ? std::max<uint64_t>(16, kc) : 16u << 10;
-  const uint64_t least = any ? floor + 1 : 256u << 10;  // the span that defers
+  const uint64_t floor = kc > 0 ? std::max<uint64_t>(16, kc) : kLongFloor;
+  const uint64_t least = any ? floor + 1 : kLongSpan;  // the span that defers
   uint64_t cap = any ? b.count : std::min<uint64_t>(b.count, device_mem_cached() / least);
   if (knob(Knob::LongList) > 0) cap = std::min<uint64_t>(cap, knob(Knob::LongList));
   cap = std::max<uint64_t>(cap, 1);
@@ -417,25 +416,26 @@ hipError_t run_ragged_long(int mode, const BatchDev &b, const DevTables &t, cons
   uint64_t *rec = nullptr;
   hipError_t e = long_record_device(&rec);
   if (e != hipSuccess) return e;
-  if ((e = scratch_malloc((void **)&bd.defer, long_ragged_bytes(mode, cap, lanes), st)) != hipSuccess) return e;
+  Scratch<unsigned long long> defer;
+  if ((e = defer.alloc(long_ragged_bytes(mode, cap, lanes), st)) != hipSuccess) return e;
+  bd.defer = defer.get();
   e = launch_long_defer_init(bd.defer, cap, st);
   if (e == hipSuccess)
     e = lit ? launch_lit_find(mode, bd, iter, out, st) : launch_dfa_fwd(mode, bd, t.f, t.r, out, st, dfa_grid);
   if (e == hipSuccess) e = launch_long_ragged(mode, bd, cap, iter, t.r, floor, kc <= 0, lanes, rec, out, st, t.cus);
   if (e == hipSuccess) e = note_long_units(st);
-  const hipError_t e2 = scratch_free(bd.defer, st);
-  return e != hipSuccess ? e : e2;
+  return e;
 }
 
-hipError_t run_lit_find(int mode, rure *re, const BatchDev &b, const DevTables &t, const FwdDfaDev &lit, void *out,
-                        hipStream_t st) {
+static hipError_t run_lit_find(int mode, rure *re, const BatchDev &b, const DevTables &t, const FwdDfaDev &lit,
+                               void *out, hipStream_t st) {
   if (ragged_long_iter(re, b, t)) return run_ragged_long(mode, b, t, lit, true, out, st, 0);
   if (b.offs) note_long_none();
   return launch_lit_find(mode, b, lit, out, st);
 }
 
-hipError_t run_regex(int mode, const BatchDev &b, const DevTables &t, void *out, hipStream_t st, int dfa_grid,
-                     const FwdDfaDev *iter) {
+static hipError_t run_regex(int mode, const BatchDev &b, const DevTables &t, void *out, hipStream_t st, int dfa_grid,
+                            const FwdDfaDev *iter = nullptr) {
   if (lane_search_ok(t)) return run_lane_search(mode, b, t, out, st);
   if (knob(Knob::Lazy) == 1 && lazy_batch(b, t))
     return run_lazy(mode, b, t, out, st);
@@ -447,37 +447,32 @@ hipError_t run_regex(int mode, const BatchDev &b, const DevTables &t, void *out,
     return launch_long_scan(mode, b, *iter, t.r, chunk, out, st, t.cus);
   // an offset batch comes with the find_iter automaton only from ragged_long_iter
   if (iter && b.offs) return run_ragged_long(mode, b, t, *iter, false, out, st, dfa_grid);
-  if (!t.quit_possible) return run_dfa_step(mode, b, t, out, st, dfa_grid, nullptr);
-  // the DFA kernels flag a quit; the Pike VM fallback returns at once without
-  BatchDev bq = b;
-  hipError_t e = scratch_malloc((void **)&bq.quit_flag, 4, st);
-  if (e == hipSuccess) e = hipMemsetAsync(bq.quit_flag, 0, 4, st);
-  if (e == hipSuccess) e = run_dfa_step(mode, bq, t, out, st, dfa_grid, nullptr);
-  if (e == hipSuccess) e = run_pike(mode, true, bq, t, out, st);
-  if (bq.quit_flag) {
-    hipError_t e2 = scratch_free(bq.quit_flag, st);
-    if (e == hipSuccess) e = e2;
-  }
-  return e;
+  const auto step = [&](const BatchDev &bq) { return run_dfa_step(mode, bq, t, out, st, dfa_grid, nullptr); };
+  return t.quit_possible ? with_quit_fallback(mode, b, t, out, st, step) : step(b);
 }
 
 
 // exec.rs:998-1038 many_matches_at for a batch.
-hipError_t run_set(const BatchDev &b, const DevTables &t, uint64_t *out, hipStream_t st, int dfa_grid) {
+static hipError_t run_set(const BatchDev &b, const DevTables &t, uint64_t *out, hipStream_t st, int dfa_grid) {
   if (!t.has_dfa) return run_pike(MODE_SET, false, b, t, out, st);
-  if (!t.quit_possible)
-    return t.use_cores ? launch_set_cores(b, t.c, out, st, t.cus) : launch_dfa_set(b, t.s, out, st, dfa_grid);
-  BatchDev bq = b;  // quit flag: see run_regex
-  hipError_t e = scratch_malloc((void **)&bq.quit_flag, 4, st);
-  if (e == hipSuccess) e = hipMemsetAsync(bq.quit_flag, 0, 4, st);
-  if (e == hipSuccess)
-    e = t.use_cores ? launch_set_cores(bq, t.c, out, st, t.cus) : launch_dfa_set(bq, t.s, out, st, dfa_grid);
-  if (e == hipSuccess) e = run_pike(MODE_SET, true, bq, t, out, st);
-  if (bq.quit_flag) {
-    hipError_t e2 = scratch_free(bq.quit_flag, st);
-    if (e == hipSuccess) e = e2;
-  }
-  return e;
+  const auto step = [&](const BatchDev &bq) {
+    return t.use_cores ? launch_set_cores(bq, t.c, out, st, t.cus) : launch_dfa_set(bq, t.s, out, st, dfa_grid);
+  };
+  return t.quit_possible ? with_quit_fallback(MODE_SET, b, t, out, st, step) : step(b);
+}
+
+// The captures Pike VM's grid over `units` waves of work (haystacks, or
+// matches), and the scratch its waves need where their working set does not
+// fit the LDS (*scratch stays empty where it does).
+static hipError_t caps_grid(size_t units, const DevTables &t, uint32_t ns, hipStream_t st, int *grid,
+                            Scratch<> *scratch) {
+  const size_t wb = caps_wave_bytes(t.n.nleaves, ns);
+  const bool in_lds = wb <= kNfaLdsMax;
+  const size_t per_cu = in_lds ? std::max<size_t>(1, std::min<size_t>(32, (160u * 1024u) / wb)) : 4;
+  size_t g = std::min<size_t>(units, (size_t)t.cus * per_cu);
+  if (!in_lds) g = std::min<size_t>(g, (256u << 20) / wb);  // bound the scratch (wide programs: MiBs per wave)
+  *grid = (int)std::max<size_t>(1, g);
+  return in_lds ? hipSuccess : scratch->alloc(wb * (size_t)*grid, st);
 }
 
 // exec.rs:524-596 read_captures_at for a batch.  One group (two slots): the
@@ -491,26 +486,19 @@ hipError_t run_captures(const BatchDev &b, const DevTables &t, uint64_t *slots, 
                         int dfa_grid) {
   if (ns <= 2) return run_regex(MODE_FIND, b, t, slots, st, dfa_grid);
   hipError_t e = hipSuccess;
-  uint64_t *found = nullptr;
+  Scratch<uint64_t> found;
   if (!t.n.anchored) {
-    if ((e = scratch_malloc((void **)&found, b.count * 16, st)) != hipSuccess) return e;
-    e = lane_search_ok(t) ? launch_lane_search(MODE_FIND, b, t.m, t.f, t.r, found, st, t.cus)
-        : t.has_dfa       ? run_dfa_step(MODE_FIND, b, t, found, st, dfa_grid, nullptr)
-                          : run_pike(MODE_FIND, false, b, t, found, st);
+    if ((e = found.alloc(b.count * 16, st)) != hipSuccess) return e;
+    e = lane_search_ok(t) ? launch_lane_search(MODE_FIND, b, t.m, t.f, t.r, found.get(), st, t.cus)
+        : t.has_dfa       ? run_dfa_step(MODE_FIND, b, t, found.get(), st, dfa_grid, nullptr)
+                          : run_pike(MODE_FIND, false, b, t, found.get(), st);
   }
-  const size_t wb = caps_wave_bytes(t.n.nleaves, ns);
-  const bool in_lds = wb <= kNfaLdsMax;
-  const size_t per_cu = in_lds ? std::max<size_t>(1, std::min<size_t>(32, (160u * 1024u) / wb)) : 4;
-  size_t g = std::min<size_t>(b.count, (size_t)t.cus * per_cu);
-  if (!in_lds) g = std::min<size_t>(g, (256u << 20) / wb);  // bound the scratch (wide programs: MiBs per wave)
-  const int grid = (int)std::max<size_t>(1, g);
-  void *scratch = nullptr;
-  if (e == hipSuccess && !in_lds) e = scratch_malloc(&scratch, wb * (size_t)grid, st);
+  int grid = 1;
+  Scratch<> scratch;
+  if (e == hipSuccess) e = caps_grid(b.count, t, ns, st, &grid, &scratch);
   if (e == hipSuccess)
-    e = launch_captures(b, t.n, found, slots, ns, scratch, found && t.skip_on && !lane_search_ok(t) ? &t.sk : nullptr,
-                        t.r, st, grid);
-  if (scratch) { hipError_t e2 = scratch_free(scratch, st); if (e == hipSuccess) e = e2; }
-  if (found) { hipError_t e2 = scratch_free(found, st); if (e == hipSuccess) e = e2; }
+    e = launch_captures(b, t.n, found.get(), slots, ns, scratch.get(),
+                        found && t.skip_on && !lane_search_ok(t) ? &t.sk : nullptr, t.r, st, grid);
   return e;
 }
 
@@ -521,20 +509,13 @@ hipError_t run_captures(const BatchDev &b, const DevTables &t, uint64_t *slots, 
 hipError_t run_captures_iter(const BatchDev &b, const DevTables &t, const IterBufs &ib, uint64_t limit, uint64_t *rows,
                              uint32_t ns, uint8_t *diverged, hipStream_t st) {
   if (ib.nm == 0) return hipSuccess;
-  const size_t wb = caps_wave_bytes(t.n.nleaves, ns);
-  const bool in_lds = wb <= kNfaLdsMax;
-  const size_t per_cu = in_lds ? std::max<size_t>(1, std::min<size_t>(32, (160u * 1024u) / wb)) : 4;
-  size_t g = std::min<size_t>(ib.nm, (size_t)t.cus * per_cu);
-  if (!in_lds) g = std::min<size_t>(g, (256u << 20) / wb);
-  const int grid = (int)std::max<size_t>(1, g);
-  void *scratch = nullptr;
-  hipError_t e = hipSuccess;
-  if (!in_lds) e = scratch_malloc(&scratch, wb * (size_t)grid, st);
+  int grid = 1;
+  Scratch<> scratch;
+  hipError_t e = caps_grid(ib.nm, t, ns, st, &grid, &scratch);
   if (e == hipSuccess)
-    e = launch_captures_iter(b, t.n, ib.moff, ib.m, ib.nm, limit, rows, ns, diverged, scratch,
+    e = launch_captures_iter(b, t.n, ib.moff.get(), ib.m.get(), ib.nm, limit, rows, ns, diverged, scratch.get(),
                              t.has_dfa && t.quit_possible && !lane_search_ok(t) ? &t.f : nullptr,
                              t.skip_on ? &t.sk : nullptr, t.r, st, grid);
-  if (scratch) { hipError_t e2 = scratch_free(scratch, st); if (e == hipSuccess) e = e2; }
   return e;
 }
 
@@ -617,7 +598,7 @@ uint64_t set_single_call(rure_set *rs, const uint8_t *hay, size_t len, size_t st
 // literals, on batches of many haystacks (few long ones keep the chunked DFA
 // scan).  RURE_AMD_LIT=1 / 0 forces it on / off.
 static constexpr size_t kLitFindMax = 8;
-const FwdDfaDev *literal_engine(int mode, rure *re, DevTables &t, const BatchDev &b) {
+static const FwdDfaDev *literal_engine(int mode, rure *re, DevTables &t, const BatchDev &b) {
   uint64_t chunk;
   const long long env = knob(Knob::Lit);
   if (env >= 0 && env != 1) return nullptr;
@@ -635,6 +616,25 @@ const FwdDfaDev *literal_engine(int mode, rure *re, DevTables &t, const BatchDev
   return fi && fi->lit_n ? fi : nullptr;
 }
 
+// rure_amd_find_batch / _is_match_batch / _shortest_match_batch: `out` holds
+// the mode's record per haystack.  The literal engine is asked for find and
+// is_match only.
+int search_batch(int mode, rure *re, const rure_amd_batch *batch, void *out, hipStream_t st) {
+  BatchDev b;
+  if (!re || !to_batch(batch, &b) || (!out && b.count)) return RURE_AMD_ERR_ARG;
+  if (b.count == 0) return RURE_AMD_OK;
+  std::string err;
+  DevTables *t = regex_device(re, &err);
+  if (!t) return err.rfind("HIP", 0) == 0 ? RURE_AMD_ERR_HIP : RURE_AMD_ERR_DFA;
+  if (const FwdDfaDev *lit = mode == MODE_SHORTEST ? nullptr : literal_engine(mode, re, *t, b))
+    return run_lit_find(mode, re, b, *t, *lit, out, st) == hipSuccess ? RURE_AMD_OK : RURE_AMD_ERR_HIP;
+  const int grid = grid_for(b.count, t->f.lds_bytes, t->cus);
+  uint64_t chunk;
+  const FwdDfaDev *iter = long_batch(mode, b, *t, &chunk) ? iter_device(re, *t, &err) : ragged_long_iter(re, b, *t);
+  if (b.offs && !iter) note_long_none();
+  return run_regex(mode, b, *t, out, st, grid, iter) == hipSuccess ? RURE_AMD_OK : RURE_AMD_ERR_HIP;
+}
+
 
 // One set of at most 64 patterns (>= 2) into one mask word per haystack.
 int set_batch_word(rure_set *rs, const BatchDev &b, uint64_t *mask, hipStream_t stream) {
@@ -648,47 +648,30 @@ int set_batch_word(rure_set *rs, const BatchDev &b, uint64_t *mask, hipStream_t 
 }
 
 // Group g (patterns [64 g, 64 g + len)) into word g of mask (words per haystack).
-int device_cus_cached() {
-  int d = 0;
-  (void)hipGetDevice(&d);
-  static std::mutex mu;
-  static std::map<int, int> cache;
-  std::lock_guard<std::mutex> g(mu);
-  auto it = cache.find(d);
-  if (it != cache.end()) return it->second;
-  return cache[d] = device_cus(d);
-}
-
-
 int set_batch_group(rure_set *g, const rure_amd_batch *batch, const BatchDev &b, uint64_t *mask, size_t words,
                     size_t w, hipStream_t st) {
-  void *tmp = nullptr;
+  Scratch<> tmp;
   const bool single = g->single != nullptr;
-  if (scratch_malloc(&tmp, b.count * (single ? 1 : 8), st) != hipSuccess) return RURE_AMD_ERR_HIP;
-  int rc = single ? rure_amd_is_match_batch(g->single, batch, (uint8_t *)tmp, st)
-                  : set_batch_word(g, b, (uint64_t *)tmp, st);
+  if (tmp.alloc(b.count * (single ? 1 : 8), st) != hipSuccess) return RURE_AMD_ERR_HIP;
+  int rc = single ? rure_amd_is_match_batch(g->single, batch, (uint8_t *)tmp.get(), st)
+                  : set_batch_word(g, b, (uint64_t *)tmp.get(), st);
   if (rc == RURE_AMD_OK &&
-      launch_mask_column(single ? (const uint8_t *)tmp : nullptr, single ? nullptr : (const uint64_t *)tmp, b.count,
-                         mask, words, w, st) != hipSuccess)
+      launch_mask_column(single ? (const uint8_t *)tmp.get() : nullptr, single ? nullptr : (const uint64_t *)tmp.get(),
+                         b.count, mask, words, w, st) != hipSuccess)
     rc = RURE_AMD_ERR_HIP;
-  if (scratch_free(tmp, st) != hipSuccess && rc == RURE_AMD_OK) rc = RURE_AMD_ERR_HIP;
   return rc;
 }
 
-
-
-// Scratch released (stream-ordered) when the scope ends, whichever return is taken.
-struct ScratchHold {
-  void *p = nullptr;
-  hipStream_t st = nullptr;
-  ~ScratchHold() { (void)scratch_free(p, st); }
-};
+// knob iter_chunk: the find_iter unit size in bytes (tests: many boundaries)
+static uint64_t iter_chunk_knob(uint64_t chunk) {
+  return knob(Knob::IterChunk) > 0 ? std::max<uint64_t>(16, knob(Knob::IterChunk)) : chunk;
+}
 
 // The unit geometry of an offset batch (documents of their own lengths) in
 // the chunked find_iter.  One unit per haystack (rag->uoff stays null) unless
 // a haystack is long: one 64 MiB document among short ones would be iterated
 // by a single lane.  The longest and the total span are reduced on the
-// device and read back (16 bytes, one synchronisation); from 256 KiB (the
+// device and read back (16 bytes, one synchronisation); from kLongSpan (the
 // threshold of long_batch and the suffix iteration) the batch is cut into
 // units of about total / lanes-in-flight bytes, a haystack shorter than that
 // keeping its one unit (iter_device.hpp Geo::uoff), and the unit total is read
@@ -696,29 +679,26 @@ struct ScratchHold {
 // sized by the units there are.  Knob iter_ragged: 0 never, 2 at any length
 // (tests, with iter_chunk: many boundaries).
 static hipError_t ragged_plan(const BatchDev &b, int cus, hipStream_t st, uint64_t *chunk, IterRagged *rag,
-                              ScratchHold *hold) {
+                              Scratch<uint64_t> *hold) {
   rag->uoff = nullptr;
   const long long mode = knob(Knob::IterRagged);
   if (mode == 0) return hipSuccess;
   hipError_t e;
   uint64_t span[2] = {0, 0};  // longest, total
-  {
-    ScratchHold stats{nullptr, st};
-    if ((e = scratch_malloc(&stats.p, 16, st)) != hipSuccess) return e;
-    if ((e = launch_iter_span_stats(b, (uint64_t *)stats.p, st, cus)) != hipSuccess) return e;
-    if ((e = hipMemcpyAsync(span, stats.p, 16, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
-  }
-  if (mode != 2 && span[0] < (256u << 10)) return hipSuccess;
-  // the fixed-stride rule's lanes in flight, over the batch's bytes
-  uint64_t per_cu = 1024;
-  if (knob(Knob::IterLanes) > 0) per_cu = std::max<uint64_t>(64, knob(Knob::IterLanes));
-  uint64_t c = odd_lines(std::max<uint64_t>(4096, span[1] / ((uint64_t)cus * per_cu)));
-  if (knob(Knob::IterChunk) > 0) c = std::max<uint64_t>(16, knob(Knob::IterChunk));
+  Scratch<uint64_t> stats;
+  if ((e = stats.alloc(16, st)) != hipSuccess) return e;
+  if ((e = launch_iter_span_stats(b, stats.get(), st, cus)) != hipSuccess) return e;
+  if ((e = hipMemcpyAsync(span, stats.get(), 16, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+  if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
+  stats.reset();  // before the units' scratch
+  if (mode != 2 && span[0] < kLongSpan) return hipSuccess;
+  // The fixed-stride rule's lanes in flight over the batch's bytes.  Kept from
+  // before: this one site divides rounding down.
+  const uint64_t c = iter_chunk_knob(
+      unit_bytes(span[1], 1, lanes_in_flight(cus, Knob::IterLanes), kIterFloor, true, Share::RoundDown));
   const size_t n = b.count + 1;
-  hold->st = st;
-  if ((e = scratch_malloc(&hold->p, 2 * n * 8, st)) != hipSuccess) return e;
-  uint64_t *nk = (uint64_t *)hold->p, *uoff = nk + n;
+  if ((e = hold->alloc(2 * n * 8, st)) != hipSuccess) return e;
+  uint64_t *nk = hold->get(), *uoff = nk + n;
   if ((e = launch_iter_ragged_units(b, c, nk, uoff, st)) != hipSuccess) return e;
   uint64_t nunits = 0;
   if ((e = hipMemcpyAsync(&nunits, uoff + b.count, 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
@@ -728,39 +708,156 @@ static hipError_t ragged_plan(const BatchDev &b, int cus, hipStream_t st, uint64
   return hipSuccess;
 }
 
+// ------------------------------------------------- the batched find_iter
+// run_find_iter's steps, in the order it tries them.
+
+// DfaAnchoredReverse regexes match only at the end of the text, so the
+// iteration (re_trait.rs:197-221) yields at most the first search's match
+// (the next search starts at the end, where an empty match is the one just
+// reported or skipped).  Searched from `start` > 0, that first search is
+// the reverse DFA over text[start..] (its look-behind differs from the
+// forward scan's); from 0 the chunked path answers the same.
+static hipError_t find_iter_anchored_rev(const DevTables &t, const BatchDev &b, const IterOut &o, hipStream_t st) {
+  Scratch<uint64_t> found;
+  hipError_t e = found.alloc(b.count * 16, st);
+  if (e != hipSuccess) return e;
+  e = run_regex(MODE_FIND, b, t, found.get(), st, grid_for(b.count, t.r.lds_bytes, t.cus));
+  if (e == hipSuccess) e = launch_find_to_iter(found.get(), b.count, o.counts, o.matches, o.cap, o.total, st);
+  return e;
+}
+
+// DfaSuffix over few long haystacks: the iteration over suffix occurrences
+// in parallel (launch_suffix_iter); RURE_AMD_SUFFIX_ITER=0 keeps the wave
+// path, =2 takes it at any length with 128-byte units (tests).
+// (a DFA that can quit: the path gives up on the first quit, the wave path
+// then runs with its Pike VM fallback)
+// hipErrorNotSupported: not this path's batch, or it gave up.
+static hipError_t find_iter_suffix(const DevTables &t, const BatchDev &b, const IterOut &o, hipStream_t st) {
+  if (t.m.mt != MT_DFA_SUFFIX || !t.lcs_free || b.offs || !b.count || b.count >= (uint64_t)t.cus * 16 ||
+      b.length <= b.start)
+    return hipErrorNotSupported;
+  const uint64_t span = b.length - b.start;
+  const bool forced = knob(Knob::SuffixIter) == 2;
+  if (knob(Knob::SuffixIter) == 0 || (span < kLongSpan && !forced)) return hipErrorNotSupported;
+  return launch_suffix_iter(b, t.m, t.f, t.r, suffix_unit_bytes(span, b.count, t.cus, forced), o, st, t.cus);
+}
+
+// What the engines of the chunked iteration are called with.
+struct IterCall {
+  rure *re;
+  DevTables *t;
+  const BatchDev &b;
+  const IterOut &o;
+  hipStream_t st;
+  std::string *err;
+  uint64_t chunk = ~0ull >> 2;
+  IterRagged ragged{};
+  Scratch<uint64_t> ragged_buf;
+  const IterRagged *rag() const { return ragged.uoff ? &ragged : nullptr; }
+};
+
+// The geometry: the fixed-stride unit (the span over the haystack's share of
+// the lanes in flight: 16 waves per CU, tools/iter_sweep.py), or for offset
+// batches the ragged geometry when a haystack is long (ragged_plan).
+static hipError_t find_iter_geometry(IterCall &c, const IterSpan *sp) {
+  const BatchDev &b = c.b;
+  const uint64_t lim = sp ? std::min<uint64_t>(b.length, sp->hi) : b.length;
+  if (!b.offs && lim > b.start && b.count)
+    c.chunk = iter_chunk_knob(
+        unit_bytes(lim - b.start, b.count, lanes_in_flight(c.t->cus, Knob::IterLanes), kIterFloor));
+  if (b.offs && !sp && b.count) return ragged_plan(b, c.t->cus, c.st, &c.chunk, &c.ragged, &c.ragged_buf);
+  return hipSuccess;
+}
+
+// A regex that is one class repeated (C+: [a-z]+, (?-u)\w+, and Unicode
+// classes \w+, \S+, \pL+ over UTF-8): its matches are the maximal runs
+// (run_iter.hip), no DFA walk; the ASCII shadow's class (an ASCII-only
+// class in Unicode mode) answers ASCII text and quits on any other
+// byte.  Knob runs=0 keeps the DFA paths (A/B).
+// True: the call is answered (*e its result, `path` noted); false: the
+// engine does not take the batch, or it quit (*quit).
+static bool find_iter_runs(const IterCall &c, const uint8_t *cls, const uint32_t *cp, bool can_quit,
+                           rure_amd_path path, hipError_t *e, bool *quit) {
+  *quit = false;
+  *e = launch_find_iter_runs(c.b, cls, cp, c.o, c.st, c.t->cus, can_quit, quit);
+  if (*e == hipErrorNotSupported || (*e == hipSuccess && *quit)) return false;
+  if (*e == hipSuccess) note_fwd_path(path);
+  return true;
+}
+
+// The ASCII shadow (all-rows LDS tables; a non-ASCII byte quits and the full
+// automaton re-runs the batch, still chunked).  True: the call is answered
+// (*e its result); false: there is no shadow, or it quit (*quit) and the
+// full automaton answers.
+static bool find_iter_shadow(const IterCall &c, const FwdDfaDev &fi, bool runs, hipError_t *e, bool *quit) {
+  *quit = false;
+  const FwdDfaDev *fa = iter_ascii_device(c.re, *c.t, c.err);
+  if (!fa) return false;
+  const DevTables &t = *c.t;
+  bool q = false;
+  if (runs && fa->run_cls && find_iter_runs(c, fa->run_cls, nullptr, true, RURE_AMD_PATH_ITER_RUNS_ASCII, e, &q))
+    return true;
+  // The full automaton cannot quit: both passes are enqueued, the
+  // shadow's quit staying a device word -- its passes after the quit
+  // check run while the word is 0, the full automaton's while it is set
+  // (nothing read back, the call only enqueues).  Knob shadow_sync=1
+  // reads the quit back.
+  if (!fi.can_quit && knob(Knob::ShadowSync) != 1) {
+    Scratch<uint32_t> qf;
+    *e = qf.alloc(8, c.st);
+    if (*e == hipSuccess) *e = hipMemsetAsync(qf.get(), 0, 4, c.st);
+    if (*e == hipSuccess)
+      *e = launch_find_iter_chunked(c.b, *fa, t.r, c.chunk, c.o, c.st, t.cus, IterQuit::device_word(qf.get()), nullptr,
+                                    c.rag());
+    if (*e == hipSuccess) {
+      BatchDev bf = c.b;
+      bf.gate = qf.get();
+      bf.gate_set = 1;
+      *e = launch_find_iter_chunked(bf, fi, t.r, c.chunk, c.o, c.st, t.cus, IterQuit::none(), nullptr, c.rag());
+    }
+    if (*e == hipSuccess) note_fwd_path(RURE_AMD_PATH_ITER_SHADOW_GATED);
+    return true;
+  }
+  *e = launch_find_iter_chunked(c.b, *fa, t.r, c.chunk, c.o, c.st, t.cus, IterQuit::read_back(quit), nullptr, c.rag());
+  if (*e == hipSuccess && *quit) return false;  // a quit: the full automaton answers
+  if (*e == hipSuccess) note_fwd_path(RURE_AMD_PATH_ITER_SHADOW);
+  return true;
+}
+
+// The full automaton.  *quit: its DFA quit and the quit was read back, the
+// one-wave-per-haystack path answers.
+static hipError_t find_iter_full(const IterCall &c, const FwdDfaDev &fi, const IterSpan *sp, bool looks,
+                                 bool shadow_quit, bool *quit) {
+  const DevTables &t = *c.t;
+  // A DFA that can quit (Unicode \b over non-ASCII bytes): the units whose
+  // searches quit are served by the wave's Pike VM inside the chunked
+  // iteration (iter_scan.hip iter_wspec_kernel .. iter_wemit_kernel;
+  // nothing read back).  Spans, and knob iter_wave=0, keep the read-back of
+  // the quit and the one-wave-per-haystack fallback.
+  if (fi.can_quit && !sp && c.re->nfa_ok && knob(Knob::IterWave) != 0) {
+    const hipError_t e = launch_find_iter_chunked(c.b, fi, t.r, c.chunk, c.o, c.st, t.cus,
+                                                  IterQuit::wave_served(&t.n), nullptr, c.rag());
+    if (e == hipSuccess) note_fwd_path(RURE_AMD_PATH_ITER_WAVE_SERVED);
+    return e;
+  }
+  const hipError_t e =
+      launch_find_iter_chunked(c.b, fi, t.r, c.chunk, c.o, c.st, t.cus, IterQuit::read_back(quit), sp, c.rag());
+  if (e == hipSuccess) {
+    if (looks)
+      note_fwd_path(*quit ? RURE_AMD_PATH_ITER_LOOKS_QUIT : RURE_AMD_PATH_ITER_LOOKS);
+    else
+      note_fwd_path(shadow_quit ? RURE_AMD_PATH_ITER_SHADOW_QUIT : RURE_AMD_PATH_ITER_CHUNKED);
+  }
+  return e;
+}
+
 // The batched find_iter (re_trait.rs:197-221) on one stream.
 hipError_t run_find_iter(rure *re, DevTables *t, const BatchDev &b, const IterOut &o, hipStream_t st,
                          std::string *err, const IterSpan *sp) {
-  // DfaAnchoredReverse regexes match only at the end of the text, so the
-  // iteration (re_trait.rs:197-221) yields at most the first search's match
-  // (the next search starts at the end, where an empty match is the one just
-  // reported or skipped).  Searched from `start` > 0, that first search is
-  // the reverse DFA over text[start..] (its look-behind differs from the
-  // forward scan's); from 0 the chunked path below answers the same.
-  if (!sp && t->anchored_rev && b.start > 0 && b.count) {
-    uint64_t *found = nullptr;
-    hipError_t e = scratch_malloc((void **)&found, b.count * 16, st);
-    if (e != hipSuccess) return e;
-    e = run_regex(MODE_FIND, b, *t, found, st, grid_for(b.count, t->r.lds_bytes, t->cus));
-    if (e == hipSuccess) e = launch_find_to_iter(found, b.count, o.counts, o.matches, o.cap, o.total, st);
-    hipError_t e2 = scratch_free(found, st);
-    return e != hipSuccess ? e : e2;
-  }
-  // DfaSuffix over few long haystacks: the iteration over suffix occurrences
-  // in parallel (launch_suffix_iter); RURE_AMD_SUFFIX_ITER=0 keeps the wave
-  // path, =2 takes it at any length with 128-byte units (tests).
-  // (a DFA that can quit: the path gives up on the first quit, the wave path
-  // then runs with its Pike VM fallback)
-  if (lane_search_ok(*t) && !sp && t->m.mt == MT_DFA_SUFFIX && t->lcs_free && !b.offs &&
-      b.count && b.count < (uint64_t)t->cus * 16 && b.length > b.start) {
-    const uint64_t span = b.length - b.start;
-    if (knob(Knob::SuffixIter) != 0 && (span >= (256u << 10) || knob(Knob::SuffixIter) == 2)) {
-      const uint64_t per_h = ((uint64_t)t->cus * 1024 + b.count - 1) / b.count;
-      const uint64_t chunk =
-          odd_lines(std::max<uint64_t>(knob(Knob::SuffixIter) == 2 ? 128 : 16u << 10, (span + per_h - 1) / per_h));
-      const hipError_t e = launch_suffix_iter(b, t->m, t->f, t->r, chunk, o, st, t->cus);
-      if (e != hipErrorNotSupported) return e;
-    }
+  if (!sp && t->anchored_rev && b.start > 0 && b.count) return find_iter_anchored_rev(*t, b, o, st);
+  if (lane_search_ok(*t) && !sp) {
+    const hipError_t e = find_iter_suffix(*t, b, o, st);
+    if (e != hipErrorNotSupported) return e;
   }
   // The reference's Literal / DfaSuffix searches (DevTables::mt_lane): every
   // search of the iteration is one of those, on a wave per haystack (lane 0
@@ -786,113 +883,19 @@ hipError_t run_find_iter(rure *re, DevTables *t, const BatchDev &b, const IterOu
   if (fi && looks && re->dfwd_iter.strip.empty()) fi = nullptr;
   bool looks_quit = false;  // the chunked pass of a look-around regex quit
   if (fi) {
-    uint64_t chunk = ~0ull >> 2;
-    const uint64_t lim = sp ? std::min<uint64_t>(b.length, sp->hi) : b.length;
-    if (!b.offs && lim > b.start && b.count) {
-      const uint64_t span = lim - b.start;
-      // lanes in flight: 16 waves per CU (tools/iter_sweep.py);
-      // RURE_AMD_ITER_LANES (per CU) overrides (tuning)
-      uint64_t per_cu = 1024;
-      if (knob(Knob::IterLanes) > 0) per_cu = std::max<uint64_t>(64, knob(Knob::IterLanes));
-      const uint64_t target = (uint64_t)t->cus * per_cu;
-      const uint64_t per_h = (target + b.count - 1) / b.count;
-      chunk = odd_lines(std::max<uint64_t>(4096, (span + per_h - 1) / per_h));
-      // knob iter_chunk: the unit size in bytes (tests: many boundaries)
-      if (knob(Knob::IterChunk) > 0) chunk = std::max<uint64_t>(16, knob(Knob::IterChunk));
-    }
-    // offset batches: the ragged geometry when a haystack is long (ragged_plan)
-    IterRagged ragged{};
-    ScratchHold ragged_buf;
-    if (b.offs && !sp && b.count) {
-      const hipError_t e = ragged_plan(b, t->cus, st, &chunk, &ragged, &ragged_buf);
-      if (e != hipSuccess) return e;
-    }
-    const IterRagged *const rag = ragged.uoff ? &ragged : nullptr;
-    // A regex that is one class repeated (C+: [a-z]+, (?-u)\w+, and Unicode
-    // classes \w+, \S+, \pL+ over UTF-8): its matches are the maximal runs
-    // (run_iter.hip), no DFA walk; the ASCII shadow's class (an ASCII-only
-    // class in Unicode mode) answers ASCII text and quits on any other
-    // byte.  Knob runs=0 keeps the DFA paths (A/B).
+    IterCall c{re, t, b, o, st, err};
+    hipError_t e = find_iter_geometry(c, sp);
+    if (e != hipSuccess) return e;
+    // the run engine, then the ASCII shadow: not for spans (the quit is read
+    // back), and no shadow after the run engine quit (it quits on a byte >=
+    // 0x80, where the shadow would quit too)
     const bool runs = !sp && knob(Knob::Runs) != 0;
-    bool run_quit = false;
-    if (runs && fi->run_cls) {
-      bool q = false;
-      const hipError_t e = launch_find_iter_runs(b, fi->run_cls, fi->run_cp, o, st, t->cus, fi->run_quit != 0, &q);
-      if (e != hipErrorNotSupported && (e != hipSuccess || !q)) {
-        if (e == hipSuccess) note_fwd_path(RURE_AMD_PATH_ITER_RUNS);
-        return e;
-      }
-      run_quit = q;
-    }
-    // the ASCII shadow first (all-rows LDS tables; a non-ASCII byte quits
-    // and the full automaton re-runs the batch, still chunked); not for
-    // spans (the quit is read back), and not after the run engine quit (it
-    // quits on a byte >= 0x80, where the shadow would quit too)
-    bool shadow_quit = false;
-    if (!sp && !run_quit) {
-      if (const FwdDfaDev *fa = iter_ascii_device(re, *t, err)) {
-        if (runs && fa->run_cls) {
-          bool q = false;
-          const hipError_t e = launch_find_iter_runs(b, fa->run_cls, nullptr, o, st, t->cus, true, &q);
-          if (e != hipErrorNotSupported && (e != hipSuccess || !q)) {
-            if (e == hipSuccess) note_fwd_path(RURE_AMD_PATH_ITER_RUNS_ASCII);
-            return e;
-          }
-        }
-        // The full automaton cannot quit: both passes are enqueued, the
-        // shadow's quit staying a device word -- its passes after the quit
-        // check run while the word is 0, the full automaton's while it is set
-        // (nothing read back, the call only enqueues).  Knob shadow_sync=1
-        // reads the quit back.
-        if (!fi->can_quit && knob(Knob::ShadowSync) != 1) {
-          uint32_t *qf = nullptr;
-          hipError_t e = scratch_malloc((void **)&qf, 8, st);
-          if (e == hipSuccess) e = hipMemsetAsync(qf, 0, 4, st);
-          if (e == hipSuccess)
-            e = launch_find_iter_chunked(b, *fa, t->r, chunk, o, st, t->cus, IterQuit::device_word(qf), nullptr, rag);
-          if (e == hipSuccess) {
-            BatchDev bf = b;
-            bf.gate = qf;
-            bf.gate_set = 1;
-            e = launch_find_iter_chunked(bf, *fi, t->r, chunk, o, st, t->cus, IterQuit::none(), nullptr, rag);
-          }
-          if (qf) {
-            const hipError_t e2 = scratch_free(qf, st);
-            if (e == hipSuccess) e = e2;
-          }
-          if (e == hipSuccess) note_fwd_path(RURE_AMD_PATH_ITER_SHADOW_GATED);
-          return e;
-        }
-        bool q = false;
-        const hipError_t e =
-            launch_find_iter_chunked(b, *fa, t->r, chunk, o, st, t->cus, IterQuit::read_back(&q), nullptr, rag);
-        if (e != hipSuccess || !q) {
-          if (e == hipSuccess) note_fwd_path(RURE_AMD_PATH_ITER_SHADOW);
-          return e;
-        }
-        shadow_quit = true;  // a quit: the full automaton below answers
-      }
-    }
-    // A DFA that can quit (Unicode \b over non-ASCII bytes): the units whose
-    // searches quit are served by the wave's Pike VM inside the chunked
-    // iteration (iter_scan.hip iter_wspec_kernel .. iter_wemit_kernel;
-    // nothing read back).  Spans, and knob iter_wave=0, keep the read-back of
-    // the quit and the one-wave-per-haystack fallback.
-    if (fi->can_quit && !sp && re->nfa_ok && knob(Knob::IterWave) != 0) {
-      const hipError_t e =
-          launch_find_iter_chunked(b, *fi, t->r, chunk, o, st, t->cus, IterQuit::wave_served(&t->n), nullptr, rag);
-      if (e == hipSuccess) note_fwd_path(RURE_AMD_PATH_ITER_WAVE_SERVED);
+    bool run_quit = false, shadow_quit = false, quit = false;
+    if (runs && fi->run_cls &&
+        find_iter_runs(c, fi->run_cls, fi->run_cp, fi->run_quit != 0, RURE_AMD_PATH_ITER_RUNS, &e, &run_quit))
       return e;
-    }
-    bool quit = false;
-    const hipError_t e =
-        launch_find_iter_chunked(b, *fi, t->r, chunk, o, st, t->cus, IterQuit::read_back(&quit), sp, rag);
-    if (e == hipSuccess) {
-      if (looks)
-        note_fwd_path(quit ? RURE_AMD_PATH_ITER_LOOKS_QUIT : RURE_AMD_PATH_ITER_LOOKS);
-      else
-        note_fwd_path(shadow_quit ? RURE_AMD_PATH_ITER_SHADOW_QUIT : RURE_AMD_PATH_ITER_CHUNKED);
-    }
+    if (!sp && !run_quit && find_iter_shadow(c, *fi, runs, &e, &shadow_quit)) return e;
+    e = find_iter_full(c, *fi, sp, looks, shadow_quit, &quit);
     if (e != hipSuccess || !quit) return e;
     looks_quit = looks;
   }
@@ -905,13 +908,12 @@ hipError_t run_find_iter(rure *re, DevTables *t, const BatchDev &b, const IterOu
 
 
 hipError_t iter_to_device(rure *re, DevTables *t, const BatchDev &b, hipStream_t st, IterBufs *ib, std::string *err) {
-  ib->st = st;
   hipError_t e;
   const size_t n = b.count;
-  if ((e = scratch_malloc((void **)&ib->counts, (n + 1) * 8, st)) != hipSuccess) return e;
-  if ((e = scratch_malloc((void **)&ib->moff, (n + 1) * 8, st)) != hipSuccess) return e;
-  if ((e = scratch_malloc((void **)&ib->total, 8, st)) != hipSuccess) return e;
-  if ((e = hipMemsetAsync(ib->counts, 0, (n + 1) * 8, st)) != hipSuccess) return e;
+  if ((e = ib->counts.alloc((n + 1) * 8, st)) != hipSuccess) return e;
+  if ((e = ib->moff.alloc((n + 1) * 8, st)) != hipSuccess) return e;
+  if ((e = ib->total.alloc(8, st)) != hipSuccess) return e;
+  if ((e = hipMemsetAsync(ib->counts.get(), 0, (n + 1) * 8, st)) != hipSuccess) return e;
   const uint64_t bytes = b.offs ? 0 : (uint64_t)b.count * b.length;
   // first guess: the regex's density on its previous call plus an eighth,
   // else a match per 64 bytes (an overflow re-runs the search once with the
@@ -921,21 +923,20 @@ hipError_t iter_to_device(rure *re, DevTables *t, const BatchDev &b, hipStream_t
                               : bytes / 64 + 2 * n;
   cap = std::max<uint64_t>(1024, cap);
   for (int pass = 0; pass < 2; ++pass) {
-    if ((e = scratch_malloc((void **)&ib->m, cap * 16, st)) != hipSuccess) return e;
-    IterOut o{ib->counts, ib->m, cap, ib->total};
+    if ((e = ib->m.alloc(cap * 16, st)) != hipSuccess) return e;
+    IterOut o{ib->counts.get(), ib->m.get(), cap, ib->total.get()};
     if ((e = run_find_iter(re, t, b, o, st, err)) != hipSuccess) return e;
     uint64_t tot = 0;
-    if ((e = hipMemcpyAsync(&tot, ib->total, 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(&tot, ib->total.get(), 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
     ib->nm = tot;
     if (bytes >= (1u << 20)) re->iter_per_mib.store((int64_t)((double)tot / ((double)bytes / (1 << 20)) + 1),
                                                     std::memory_order_relaxed);
     if (tot <= cap) break;
-    (void)scratch_free(ib->m, st);
-    ib->m = nullptr;
+    ib->m.reset();  // before the exact-size retry
     cap = tot;
   }
-  return exclusive_scan_u64(ib->counts, ib->moff, n + 1, st);
+  return exclusive_scan_u64(ib->counts.get(), ib->moff.get(), n + 1, st);
 }
 
 
@@ -951,7 +952,7 @@ struct KmerCacheEntry {
 std::mutex g_kmer_mu;
 std::vector<KmerCacheEntry> g_kmer;
 
-bool build_kmer(rure *const *res, size_t n, std::vector<uint32_t> *bitmap, std::vector<uint16_t> *mask,
+static bool build_kmer(rure *const *res, size_t n, std::vector<uint32_t> *bitmap, std::vector<uint16_t> *mask,
                 std::vector<uint16_t> *hmask, KmerDev *km) {
   if (n == 0 || n > 16) return false;
   size_t L = 0;

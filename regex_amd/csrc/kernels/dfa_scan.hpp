@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../../include/rure_amd.h"
+#include "../host/chunk_plan.hpp"
 #include "../host/knobs.hpp"
 
 namespace rure_amd {
@@ -627,5 +628,43 @@ uint32_t lazy_dfa_hot_rows(uint32_t ncol);
 // hipFreeAsync (the memory is usable on any stream once the call returns).
 hipError_t scratch_malloc(void **p, size_t bytes, hipStream_t st);
 hipError_t scratch_free(void *p, hipStream_t st);
+
+// One scratch block, freed (stream-ordered) when its owner's scope ends,
+// whichever return is taken; reset() frees it sooner.  The status of
+// scratch_free is dropped: it fails only for a pointer that is not a scratch
+// block, which a Scratch never holds.
+template <class T = void>
+class Scratch {
+ public:
+  Scratch() = default;
+  Scratch(Scratch &&o) noexcept : p_(o.p_), st_(o.st_) { o.p_ = nullptr; }
+  Scratch &operator=(Scratch &&o) noexcept {
+    if (this != &o) {
+      reset();
+      p_ = o.p_, st_ = o.st_;
+      o.p_ = nullptr;
+    }
+    return *this;
+  }
+  Scratch(const Scratch &) = delete;
+  Scratch &operator=(const Scratch &) = delete;
+  ~Scratch() { reset(); }
+  // `bytes` of scratch for work on `st` (a block held before is freed first)
+  hipError_t alloc(size_t bytes, hipStream_t st) {
+    reset();
+    st_ = st;
+    return scratch_malloc((void **)&p_, bytes, st);
+  }
+  void reset() {
+    if (p_) (void)scratch_free(p_, st_);
+    p_ = nullptr;
+  }
+  T *get() const { return p_; }
+  explicit operator bool() const { return p_ != nullptr; }
+
+ private:
+  T *p_ = nullptr;
+  hipStream_t st_ = nullptr;
+};
 
 }  // namespace rure_amd

@@ -111,13 +111,7 @@ __global__ __launch_bounds__(1024) void long_geometry_kernel(BatchDev b, uint64_
     return;
   }
   const uint64_t total = D[kDeferTotal];
-  uint64_t c = (total + lanes - 1) / lanes;
-  if (c < floor) c = floor;
-  if (round) {
-    uint64_t lines = (c + 127) / 128;
-    if ((lines & 1) == 0) ++lines;
-    c = lines * 128;
-  }
+  const uint64_t c = unit_bytes(total, 1, lanes, floor, round != 0);
   const unsigned long long *list = D + kDeferList;
   unsigned long long *lu = D + ragged_lu_off(cap), *best = D + ragged_best_off(cap);
   unsigned long long *done = D + ragged_done_off(cap);

@@ -200,15 +200,8 @@ struct Staging {
 // exclusive sums moff (n + 1) and the match records; reads the total on the
 // host (one sync) and reruns once with an exact buffer if the guess was short.
 struct IterBufs {
-  uint64_t *counts = nullptr, *moff = nullptr, *m = nullptr, *total = nullptr;
+  Scratch<uint64_t> counts, moff, m, total;
   uint64_t nm = 0;
-  hipStream_t st = nullptr;
-  ~IterBufs() {
-    if (counts) (void)scratch_free(counts, st);
-    if (moff) (void)scratch_free(moff, st);
-    if (m) (void)scratch_free(m, st);
-    if (total) (void)scratch_free(total, st);
-  }
 };
 
 struct NfaOffsets { size_t leaves, cl_off, entries, perlw, save_off, save_slot, cl_info, cl_big, cl_boff, cl_sub; };
@@ -324,8 +317,6 @@ struct rure_iter {
 namespace rt {
 
 // ------------------------------------------------------------ build.cpp
-// ---------------------------------------------------------- dispatch.cpp
-// ----------------------------------------------------------- scratch.cpp
 uint32_t uniform_start(const DenseDfa &d);
 void build_stride_image(const DenseDfa &d, PackedFwd *p);
 bool pack_forward(const DenseDfa &d, PackedFwd *p, std::string *err, bool all = false);
@@ -361,28 +352,12 @@ bool build_shiftand(const LiteralSet &ls, std::vector<uint64_t> *mask, uint64_t 
 const FwdDfaDev *iter_ascii_device(rure *re, const DevTables &t, std::string *err);
 const FwdDfaDev *iter_device(rure *re, const DevTables &t, std::string *err);
 bool adapt_cores(rure_set *rs, DevTables *t, const BatchDev &b, hipStream_t st, std::string *err);
+bool class_one_set(const Expr &e, uint8_t cls[256]);
+// ---------------------------------------------------------- dispatch.cpp
 int device_cus(int dev);
 int grid_for(size_t count, uint32_t lds_bytes, int cus);
-int pike_grid(size_t count, bool fallback, const NfaDev &n, int cus);
-hipError_t run_pike(int mode, bool fallback, const BatchDev &b, const DevTables &t, void *out, hipStream_t st);
-uint64_t odd_lines(uint64_t bytes);
-bool long_batch(int mode, const BatchDev &b, const DevTables &t, uint64_t *chunk);
-hipError_t run_dfa_step(int mode, const BatchDev &b, const DevTables &t, void *out, hipStream_t st, int dfa_grid,
-                        const FwdDfaDev *iter);
+uint64_t lanes_in_flight(int cus, Knob k);
 bool lane_search_ok(const DevTables &t);
-bool suffix_long_ok(const BatchDev &b, const DevTables &t, uint64_t *chunk);
-hipError_t run_suffix_long(int mode, const BatchDev &b, const DevTables &t, uint64_t chunk, void *out,
-                           hipStream_t st);
-hipError_t run_lane_search(int mode, const BatchDev &b, const DevTables &t, void *out, hipStream_t st);
-bool big_batch(const BatchDev &b, const DevTables &t);
-const FwdDfaDev *ragged_long_iter(rure *re, const BatchDev &b, const DevTables &t);
-hipError_t run_ragged_long(int mode, const BatchDev &b, const DevTables &t, const FwdDfaDev &iter, bool lit, void *out,
-                           hipStream_t st, int dfa_grid);
-hipError_t run_lit_find(int mode, rure *re, const BatchDev &b, const DevTables &t, const FwdDfaDev &lit, void *out,
-                        hipStream_t st);
-hipError_t run_regex(int mode, const BatchDev &b, const DevTables &t, void *out, hipStream_t st, int dfa_grid,
-                     const FwdDfaDev *iter = nullptr);
-hipError_t run_set(const BatchDev &b, const DevTables &t, uint64_t *out, hipStream_t st, int dfa_grid);
 hipError_t run_captures(const BatchDev &b, const DevTables &t, uint64_t *slots, uint32_t ns, hipStream_t st,
                         int dfa_grid);
 hipError_t run_captures_iter(const BatchDev &b, const DevTables &t, const IterBufs &ib, uint64_t limit, uint64_t *rows,
@@ -390,19 +365,16 @@ hipError_t run_captures_iter(const BatchDev &b, const DevTables &t, const IterBu
 bool to_batch(const rure_amd_batch *b, BatchDev *o);
 bool single_call(rure *re, int mode, const uint8_t *hay, size_t len, size_t start, uint64_t *r0, uint64_t *r1);
 uint64_t set_single_call(rure_set *rs, const uint8_t *hay, size_t len, size_t start);
-const FwdDfaDev *literal_engine(int mode, rure *re, DevTables &t, const BatchDev &b);
+int search_batch(int mode, rure *re, const rure_amd_batch *batch, void *out, hipStream_t st);
 int set_batch_word(rure_set *rs, const BatchDev &b, uint64_t *mask, hipStream_t stream);
-int device_cus_cached();
 int set_batch_group(rure_set *g, const rure_amd_batch *batch, const BatchDev &b, uint64_t *mask, size_t words,
                     size_t w, hipStream_t st);
 hipError_t run_find_iter(rure *re, DevTables *t, const BatchDev &b, const IterOut &o, hipStream_t st,
                          std::string *err, const IterSpan *sp = nullptr);
 hipError_t iter_to_device(rure *re, DevTables *t, const BatchDev &b, hipStream_t st, IterBufs *ib, std::string *err);
-bool class_one_set(const Expr &e, uint8_t cls[256]);
-bool build_kmer(rure *const *res, size_t n, std::vector<uint32_t> *bitmap, std::vector<uint16_t> *mask,
-                std::vector<uint16_t> *hmask, KmerDev *km);
 bool kmer_device(rure *const *res, size_t n, KmerDev *out);
 void kmer_forget(const rure *re);
+// ----------------------------------------------------------- scratch.cpp
 void scratch_release();
 void handle_created();
 void handle_freed();
