@@ -264,12 +264,20 @@ long rure_amd_expand_template_export(rure *re, const uint8_t *rep, size_t rep_le
  * (device, 16-byte aligned, `capacity` bytes each; readable 16 bytes past
  * capacity); the result is in out0 if n is odd, else out1.  lengths (device,
  * n + 1 uint64) = length, then each step's output length.  An output longer
- * than capacity is cut; that step's length is exact, the steps after it read
- * their input cut and their lengths are lower bounds (a step never shortens
- * its text, so lengths[n] > capacity): retry with capacity = lengths[n]
- * until lengths[n] <= capacity.  Only enqueues:
- * each step's match count per 4 KiB is counted by the previous step's kernel
- * as it writes the text, and nothing is read back. */
+ * than capacity is cut and no byte at or past capacity is written.  A chain
+ * that runs as one byte map (RURE_AMD_PATH_REPLACE_HMAP: every byte's image
+ * under the whole chain is at most 64 bytes, the 256 images are at most 4096
+ * bytes together and fewer than 256 byte values change) reports every length
+ * exactly, cut or not.  Step by step (RURE_AMD_PATH_REPLACE_CLASS) the first
+ * step whose output is cut reports its length exactly, and each step after
+ * it reads exactly the `capacity` bytes its input buffer holds and reports
+ * the length of what it makes of them: a lower bound of its true length and
+ * at least capacity (a step never shortens its text), equal to capacity only
+ * if it replaced nothing.  So the result is whole if and only if no lengths[i]
+ * exceeds capacity; otherwise retry with capacity = the largest lengths[i]
+ * (each retry fits at least one more step).  Only enqueues: each step's
+ * match count per 4 KiB is counted by the previous step's kernel as it writes
+ * the text, and nothing is read back. */
 int rure_amd_replace_all_chain(rure *const *res, const uint8_t *const *reps, const size_t *rep_lens, size_t n,
                                const uint8_t *haystack, size_t length, uint8_t *out0, uint8_t *out1,
                                size_t capacity, uint64_t *lengths, void *stream);
@@ -446,6 +454,21 @@ int rure_amd_run_cp_export(rure *re, uint32_t *bits, size_t n);
  * match list (rure_amd_replace_batch, RURE_AMD_PATH_REPLACE_CLASS); 0 if
  * not. */
 int rure_amd_class_one_export(rure *re, uint8_t *cls);
+/* The byte map rure_amd_replace_all_chain composes for a chain (host only, no
+ * GPU; res, reps, rep_lens, n as there, n >= 1): the chain sends each byte x
+ * to a string F(x).  Returns 1 if the chain is mappable (runs as
+ * RURE_AMD_PATH_REPLACE_HMAP): every F(x) is at most 64 bytes, their lengths
+ * sum to at most 4096, and fewer than 256 byte values change; 0 if it runs
+ * step by step; RURE_AMD_ERR_ARG as that call.  *nact = the byte values with
+ * F(x) != x and *pool_len = the sum of the |F(x)| (both 0 when an image is
+ * longer than 64 bytes).  Only when it returns 1: flen[256] = |F(x)|,
+ * soff[256] = the offset of F(x) in the pool, aidx[256] = the index of x among
+ * the changed bytes in byte order, 0xFF if F(x) = x; pool = the strings (at
+ * most pool_cap bytes copied); dlen[i * 256 + x] = |F_i(x)| - 1, the image of
+ * x after steps 0..i.  Any array may be NULL. */
+int rure_amd_chain_map_export(rure *const *res, const uint8_t *const *reps, const size_t *rep_lens, size_t n,
+                              uint8_t *flen, uint16_t *soff, uint8_t *aidx, uint32_t *nact, uint8_t *pool,
+                              size_t pool_cap, size_t *pool_len, uint32_t *dlen);
 
 /* Export of the Pike VM closure tables the NFA kernel runs (host only):
  * leaves = 3 u32 per leaf (kind | lo << 8 | hi << 16, closure, slot),

@@ -879,8 +879,10 @@ def replace_all_chain(regexes, reps, haystack, length=None, capacity=None, strea
     are single bytes of one class, replacements of 1-64 bytes, e.g. the
     regex-dna IUB substitutions).  Only enqueues.  Returns (out, lengths):
     the final text in out[:lengths[-1]] (a device tensor of capacity + 16
-    bytes) and the n + 1 lengths (device int64).  If lengths[-1] exceeds
-    capacity the output was cut: call again with capacity >= lengths[-1]."""
+    bytes) and the n + 1 lengths (device int64).  If any length exceeds
+    capacity an output was cut: call again with capacity >= max(lengths)
+    (step by step, the lengths after a cut step are those of its cut input:
+    include/rure_amd.h)."""
     import torch
     n = len(regexes)
     length = haystack.numel() - 16 if length is None else length

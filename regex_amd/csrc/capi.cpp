@@ -6,6 +6,7 @@
 // engine construction of src/exec.rs:273-327 (three programs per regex: NFA,
 // forward DFA with `.*?`, reverse DFA).  All matching runs on the GPU.
 #include "runtime.hpp"
+#include "host/chain_map.hpp"
 #include "host/expand.hpp"
 
 namespace {
@@ -647,49 +648,21 @@ int rure_amd_replace_all_chain(rure *const *res, const uint8_t *const *reps, con
     sw[i] = {w[0], w[1]};
   }
   // The chain is a string homomorphism: compose each byte's image F(x) and
-  // its length after every step, and run it as one map (launch_replace_hmap)
-  // when the images are at most 64 bytes and fit the 4 KiB pool.
+  // its length after every step (host/chain_map.hpp), and run it as one map
+  // (launch_replace_hmap) when it is mappable: images of at most 64 bytes
+  // that fit the 4 KiB pool, and fewer than 256 changed byte values.
   if (knob(Knob::ChainSeq) != 1) {
-    std::vector<std::string> img(256);
-    std::vector<uint32_t> dl(n * 256, 0);
-    bool ok = true;
-    for (int x = 0; x < 256 && ok; ++x) {
-      std::string cur(1, (char)x);
-      for (size_t i = 0; i < n && ok; ++i) {
-        std::string nx;
-        for (unsigned char c : cur) {
-          if (res[i]->cls_one[c]) nx.append((const char *)reps[i], rep_lens[i]);
-          else nx.push_back((char)c);
-        }
-        cur.swap(nx);
-        if (cur.size() > 64) ok = false;
-        dl[i * 256 + x] = (uint32_t)cur.size() - 1;
-      }
-      img[x] = cur;
-    }
-    size_t pool = 0;
-    for (int x = 0; x < 256; ++x) pool += img[x].size();
-    if (ok && pool <= kHMapPoolMax) {
-      std::vector<uint8_t> blob(1024 + kHMapPoolMax + n * 256 * 4, 0);
-      uint16_t *so = (uint16_t *)(blob.data() + 256);
-      size_t at = 0;
-      uint32_t nact = 0;
-      for (int x = 0; x < 256; ++x) {
-        blob[x] = (uint8_t)img[x].size();
-        so[x] = (uint16_t)at;
-        const bool same = img[x].size() == 1 && (uint8_t)img[x][0] == x;
-        blob[768 + x] = same ? 0xFF : (uint8_t)nact;
-        nact += same ? 0 : 1;
-        memcpy(blob.data() + 1024 + at, img[x].data(), img[x].size());
-        at += img[x].size();
-      }
-      memcpy(blob.data() + 1024 + kHMapPoolMax, dl.data(), dl.size() * 4);
+    std::vector<const uint8_t *> cl(n);
+    for (size_t i = 0; i < n; ++i) cl[i] = res[i]->cls_one;
+    const ChainMap cm = compose_chain_map(cl.data(), reps, rep_lens, n, kHMapPoolMax);
+    if (cm.mappable) {
+      const std::vector<uint8_t> &blob = cm.blob;
       Scratch<uint8_t> db;
       hipError_t e = db.alloc(blob.size(), st);
       if (e == hipSuccess) e = hipMemcpyAsync(db.get(), blob.data(), blob.size(), hipMemcpyHostToDevice, st);
       uint8_t *out = (n & 1) ? out0 : out1;
       if (e == hipSuccess)
-        e = launch_replace_hmap(haystack, length, (int)n, db.get(), (uint32_t)pool, nact, out, capacity, lengths, st,
+        e = launch_replace_hmap(haystack, length, (int)n, db.get(), cm.pool_len, cm.nact, out, capacity, lengths, st,
                                 cus);
       if (e == hipSuccess) note_fwd_path(RURE_AMD_PATH_REPLACE_HMAP);
       if (e != hipErrorNotSupported) return e == hipSuccess ? RURE_AMD_OK : RURE_AMD_ERR_HIP;
@@ -1038,6 +1011,28 @@ int rure_amd_class_one_export(rure *re, uint8_t *cls) {
   if (!re) return RURE_AMD_ERR_ARG;
   if (re->cls_one_ok && cls) memcpy(cls, re->cls_one, 256);
   return re->cls_one_ok ? 1 : 0;
+}
+
+int rure_amd_chain_map_export(rure *const *res, const uint8_t *const *reps, const size_t *rep_lens, size_t n,
+                              uint8_t *flen, uint16_t *soff, uint8_t *aidx, uint32_t *nact, uint8_t *pool,
+                              size_t pool_cap, size_t *pool_len, uint32_t *dlen) {
+  if (!res || !reps || !rep_lens || n == 0) return RURE_AMD_ERR_ARG;
+  std::vector<const uint8_t *> cl(n);
+  for (size_t i = 0; i < n; ++i) {
+    if (!res[i] || !res[i]->cls_one_ok || !reps[i] || rep_lens[i] < 1 || rep_lens[i] > 64) return RURE_AMD_ERR_ARG;
+    cl[i] = res[i]->cls_one;
+  }
+  const ChainMap cm = compose_chain_map(cl.data(), reps, rep_lens, n, kHMapPoolMax);
+  if (nact) *nact = cm.nact;
+  if (pool_len) *pool_len = cm.pool_len;
+  if (!cm.mappable) return 0;
+  const uint8_t *b = cm.blob.data();
+  if (flen) memcpy(flen, b, 256);
+  if (soff) memcpy(soff, b + 256, 512);
+  if (aidx) memcpy(aidx, b + 768, 256);
+  if (pool) memcpy(pool, b + 1024, std::min<size_t>(pool_cap, cm.pool_len));
+  if (dlen) memcpy(dlen, b + 1024 + kHMapPoolMax, n * 256 * 4);
+  return 1;
 }
 
 int rure_amd_run_cp_export(rure *re, uint32_t *bits, size_t n) {

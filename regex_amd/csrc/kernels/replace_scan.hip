@@ -754,12 +754,15 @@ __device__ __forceinline__ uint32_t cls_count_co(const uint8_t *cls, const uint4
 
 __global__ __launch_bounds__(256) void replace_cls_count_kernel(const uint8_t *hay, uint64_t n, const uint8_t *cls_g,
                                                                 uint64_t nunits, uint64_t *ucount, uint32_t sw1,
-                                                                uint32_t sw2, const uint64_t *n_dev) {
+                                                                uint32_t sw2, const uint64_t *n_dev,
+                                                                uint64_t cap) {
   __shared__ uint8_t cls[256];
   cls[threadIdx.x] = cls_g[threadIdx.x];
   __syncthreads();
-  if (n_dev) {  // chained calls: the length on the device (n, nunits: upper bounds; units past it count 0)
-    n = *n_dev;
+  // chained calls: the length on the device (n, nunits: upper bounds; units
+  // past it count 0), cut to the cap bytes the input buffer holds
+  if (n_dev) {
+    n = min(*n_dev, cap);
     nunits = min(nunits, max<uint64_t>(1, (n + kClsUnit - 1) / kClsUnit));
   }
   const uint32_t lane = threadIdx.x & 63;
@@ -783,10 +786,11 @@ __global__ __launch_bounds__(256) void replace_cls_count_kernel(const uint8_t *h
 }
 
 // total (device) = the output length; out_offsets = {0, total} (either may
-// be null); n_dev (chained calls): the input length on the device
+// be null); n_dev (chained calls): the input length on the device, of which
+// the input buffer holds at most cap bytes (the rest was cut)
 __global__ void replace_cls_total_kernel(uint64_t n, uint64_t rep_len, const uint64_t *uoff, uint64_t nunits,
-                                         uint64_t *ooff, uint64_t *total, const uint64_t *n_dev) {
-  if (n_dev) n = *n_dev;
+                                         uint64_t *ooff, uint64_t *total, const uint64_t *n_dev, uint64_t cap) {
+  if (n_dev) n = min(*n_dev, cap);
   const uint64_t t = n + uoff[nunits] * rep_len - uoff[nunits];
   if (!ooff) {
     *total = t;
@@ -963,8 +967,8 @@ __global__ __launch_bounds__(256, CLS_WAVES) void replace_cls_write_kernel(const
   ClsWave &W = sw[threadIdx.x >> 6];
   const uint64_t nw = (uint64_t)gridDim.x * 4;
   const uint64_t ulim = nunits;  // the count arrays' units (ncnt: this output's)
-  if (n_dev) {
-    n = *n_dev;
+  if (n_dev) {  // (a chain's buffers all hold cap bytes: the input was cut there as the output is)
+    n = min(*n_dev, cap);
     nunits = min(nunits, max<uint64_t>(1, (n + kClsUnit - 1) / kClsUnit));
   }
   for (uint64_t u = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); u < nunits; u += nw) {
@@ -1003,11 +1007,15 @@ __global__ __launch_bounds__(256, CLS_WAVES) void replace_cls_write_kernel(const
       // the next substitution's class bytes in this lane's output, by 4 KiB
       // output unit (the next call's units): its text bytes outside this
       // class, plus the copies in each replacement (nrep of them); a lane
-      // whose output crosses a unit edge places them byte by byte
+      // whose output crosses a unit edge or cap places them byte by byte
+      // (the next call reads the cap bytes that are written: bytes past cap
+      // count nowhere)
       const uint64_t nm = next_mask(v, avail, nsw1, nsw2) & ~m;
       const uint64_t os = ob + r0, oe = os + len;
       uint32_t lo = 0, hi = 0;  // counts in unit os >> 12 and the one after
-      if (len == 0 || (os >> 12) == ((oe - 1) >> 12)) {
+      if (len == 0 || os >= cap) {
+        // none of this lane's output is read
+      } else if (oe <= cap && (os >> 12) == ((oe - 1) >> 12)) {
         lo = (uint32_t)__popcll(nm) + k * nrep;
       } else {
         // bytes before e1 count in the lane's first unit, before e1 + 4096 in
@@ -1015,6 +1023,7 @@ __global__ __launch_bounds__(256, CLS_WAVES) void replace_cls_write_kernel(const
         // only long replacements reach that far) take an atomic each
         const uint64_t e1 = (os | 4095) + 1;
         auto put = [&](uint64_t q) {
+          if (q >= cap) return;
           if (q < e1) ++lo;
           else if (q < e1 + 4096) ++hi;
           else if ((q >> 12) < ulim) atomicAdd(&ncnt[q >> 12], 1ull);
@@ -1610,11 +1619,11 @@ hipError_t launch_replace_class(const uint8_t *hay, uint64_t n, const uint8_t *c
   do {
     if ((e = hipMemsetAsync(ucount + nunits, 0, 8, st)) != hipSuccess) break;
     hipLaunchKernelGGL(replace_cls_count_kernel, dim3(grid), dim3(256), 0, st, hay, n, cls, nunits, ucount, sw1, sw2,
-                       (const uint64_t *)nullptr);
+                       (const uint64_t *)nullptr, (uint64_t)0);
     if ((e = hipGetLastError()) != hipSuccess) break;
     if ((e = exclusive_scan_u64(ucount, uoff, nunits + 1, st)) != hipSuccess) break;
     hipLaunchKernelGGL(replace_cls_total_kernel, dim3(1), dim3(1), 0, st, n, (uint64_t)rep_len, uoff, nunits, ooff,
-                       total, (const uint64_t *)nullptr);
+                       total, (const uint64_t *)nullptr, (uint64_t)0);
     if ((e = hipGetLastError()) != hipSuccess) break;
     if (cap) {
       hipLaunchKernelGGL(replace_cls_write_kernel, dim3(gridw), dim3(256), 0, st, hay, n, cls, nunits, uoff, rep,
@@ -1675,10 +1684,12 @@ hipError_t launch_replace_hmap(const uint8_t *in, uint64_t n, int steps, const u
 // nxt[i][0..1], when the class has at most two bytes), so only step 0 and
 // steps after a wider class run the count pass; the lengths stay on the
 // device (lengths[i + 1] = the output length of step i) and nothing is read
-// back.  Outputs past cap are cut (the lengths still count them; a step whose
-// input was cut reads garbage past cap, so the caller checks lengths[steps]
-// <= cap: replacements are never shorter than the byte they replace, so the
-// lengths only grow).
+// back.  Outputs past cap are cut: the step that overflows still reports its
+// whole length, and every step after it works on exactly the cap bytes its
+// input buffer holds (the kernels cut lengths[i] to cap and the write kernel
+// counts the next class below cap only), so its length is that of the cut
+// input's output: at least cap and at most the true length.  The chain fits
+// when no length exceeds cap.
 hipError_t launch_replace_class_chain(const uint8_t *hay, uint64_t n0, int steps, const uint8_t *const *cls,
                                       const uint8_t *const *rep, const uint32_t *rep_len, const uint32_t (*sw)[2],
                                       const uint32_t *nrep, uint8_t *out0, uint8_t *out1, uint64_t cap,
@@ -1711,7 +1722,7 @@ hipError_t launch_replace_class_chain(const uint8_t *hay, uint64_t n0, int steps
       if (!counted) {
         if ((e = hipMemsetAsync(c, 0, (nunits + 1) * 8, st)) != hipSuccess) break;
         hipLaunchKernelGGL(replace_cls_count_kernel, dim3(grid), dim3(256), 0, st, in, n, cls[i], nunits, c,
-                           sw[i][0], sw[i][1], n_dev);
+                           sw[i][0], sw[i][1], n_dev, cap);
         if ((e = hipGetLastError()) != hipSuccess) break;
       }
       if ((e = exclusive_scan_u64(c, uoff, nunits + 1, st)) != hipSuccess) break;
@@ -1723,7 +1734,7 @@ hipError_t launch_replace_class_chain(const uint8_t *hay, uint64_t n0, int steps
                          chain ? (unsigned long long *)cn : (unsigned long long *)nullptr);
       if ((e = hipGetLastError()) != hipSuccess) break;
       hipLaunchKernelGGL(replace_cls_total_kernel, dim3(1), dim3(1), 0, st, n, (uint64_t)rep_len[i], uoff, nunits,
-                         (uint64_t *)nullptr, lengths + i + 1, n_dev);
+                         (uint64_t *)nullptr, lengths + i + 1, n_dev, cap);
       e = hipGetLastError();
       counted = chain;
     }

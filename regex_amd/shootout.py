@@ -76,16 +76,17 @@ class RegexDna(object):
         res = find_iter_span_multi(self.variants, stripped, 0, clen, length=clen, capacities=[1 << 16] * 9,
                                    stream=stream)
         counts = [int(c.item()) for c, _, _ in res]
-        # the 11 substitutions in one enqueue; the final length is the one
-        # read-back (a cut output, lengths[-1] > capacity, reruns sized
-        # exactly; the IUB codes grow the stream by a third, so twice its
+        # the 11 substitutions in one enqueue; the lengths are the one
+        # read-back (a cut output, some length > capacity, reruns with the
+        # largest; the IUB codes grow the stream by a third, so twice its
         # length is never cut)
         cap = 2 * clen + 4096
         while True:
             _, lengths = replace_all_chain([r for r, _ in self.substs], [t for _, t in self.substs], stripped,
                                            length=clen, capacity=cap, stream=stream)
-            sl = int(lengths[-1].item())
-            if sl <= cap:
+            ln = lengths.tolist()
+            sl = ln[-1]
+            if max(ln) <= cap:
                 break
-            cap = sl
+            cap = max(ln)
         return {"counts": counts, "ilen": n, "clen": clen, "slen": sl}
