@@ -123,7 +123,20 @@ const char *rure_error_message(rure_error *err);
  * The kernels load whole aligned 16-byte blocks: the buffer must be readable
  * up to the 16-byte-rounded end of its last haystack (device allocations of
  * the HIP runtime and torch are); bytes outside a haystack never influence
- * its results. */
+ * its results.  `haystack` may have any alignment and `stride` any value:
+ * some engines need a 16-byte-aligned base and stride, and a batch that is not
+ * so placed takes another kernel with the same results.
+ *
+ * Outputs.  Record outputs (`rure_match *`, the uint64_t / size_t arrays:
+ * out, end, mask, counts, matches, pieces, slots, records, total) need the
+ * alignment of their element type, 8 bytes; no call needs more of them.  The
+ * byte output `out` of rure_amd_replace_batch must be 16-byte aligned, that
+ * of rure_amd_replace_expand_batch may have any alignment.  An output with a
+ * `capacity` receives at most that many records (bytes for `out_capacity`):
+ * nothing at or past it is written, so the buffer needs no slack, and the
+ * counts, offsets and totals reported are exact whatever the capacity is
+ * (it never changes the records that are written either).  With capacity 0
+ * the output pointer may be NULL. */
 typedef struct rure_amd_batch {
   const uint8_t *haystack;
   const uint64_t *offsets;
@@ -214,9 +227,11 @@ int rure_amd_find_iter_span_multi(rure *const *res, size_t n, const uint8_t *hay
  * `limit` matches (0 = all) of the batched find_iter are replaced by
  * rep[0..rep_len) (host memory; `$` is not expanded, as with NoExpand).
  * out_offsets (device, n + 1) = the output layout (exclusive sums of the
- * output lengths); out (device) receives the concatenated outputs, at most
- * out_capacity bytes; *total (device) = the bytes needed (call again with a
- * larger buffer if it exceeds out_capacity).  Synchronises the stream once
+ * output lengths); out (device, 16-byte aligned: RURE_AMD_ERR_ARG otherwise,
+ * nothing launched) receives the concatenated outputs, at most out_capacity
+ * bytes: no byte at or past out_capacity is written; *total (device) = the
+ * bytes needed (call again with a larger buffer if it exceeds
+ * out_capacity).  Synchronises the stream once
  * to size the match buffer (twice if the first guess was short), except for
  * replace_all (limit 0) of a regex whose matches are single bytes of one
  * class over one fixed-stride haystack, which only enqueues. */
@@ -225,11 +240,12 @@ int rure_amd_replace_batch(rure *re, const rure_amd_batch *batch, const uint8_t 
                            uint64_t *total, void *stream);
 /* Batched replacen with a `$`-expanding template (bytes::Regex::replacen's
  * captures path, re_bytes.rs:513-535): as rure_amd_replace_batch (out,
- * out_offsets, out_capacity, total, limit: the same contract; batch->start
- * must be 0), but rep[0..rep_len) is expanded per match as expand.rs:50-110
- * does: `$N`, `$name`, `${...}` name a group (the longest run of
- * [0-9A-Za-z_] after the `$`: `$1a` is the group named "1a"), `$$` is a `$`,
- * an unknown group or one that did not participate expands to nothing.
+ * out_offsets, out_capacity, total, limit: the same contract, except that
+ * out may have any alignment; batch->start must be 0), but rep[0..rep_len)
+ * is expanded per match as expand.rs:50-110 does: `$N`, `$name`, `${...}`
+ * name a group (the longest run of [0-9A-Za-z_] after the `$`: `$1a` is the
+ * group named "1a"), `$$` is a `$`, an unknown group or one that did not
+ * participate expands to nothing.
  * diverged (device, n bytes) as for rure_amd_captures_iter_batch, over the
  * first `limit` matches of each haystack only: the output range
  * [out_offsets[i], out_offsets[i + 1]) of a haystack with diverged[i] != 0 is

@@ -515,7 +515,7 @@ class Regex(object):
         div = torch.zeros((max(b.count, 1),), dtype=torch.uint8, device=dev)[:b.count]
         cap = haystack.numel() + 1024
         while True:
-            out = torch.empty((max(cap, 16) + 16,), dtype=torch.uint8, device=dev)
+            out = torch.empty((max(cap, 1),), dtype=torch.uint8, device=dev)  # (no slack: the cut is exact)
             if expanding:
                 _check(N.rure_amd_replace_expand_batch(
                     self._re, ctypes.byref(b), rep, len(rep), limit, ctypes.c_void_p(out.data_ptr()),

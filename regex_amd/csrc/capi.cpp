@@ -695,6 +695,8 @@ int rure_amd_replace_batch(rure *re, const rure_amd_batch *batch, const uint8_t 
   BatchDev b;
   if (!re || !to_batch(batch, &b) || !out_offsets || !total || (!out && out_capacity) || (!rep && rep_len))
     return RURE_AMD_ERR_ARG;
+  // the copy kernels store whole aligned 16-byte blocks of the output
+  if ((uintptr_t)out & 15) return RURE_AMD_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   if (b.count == 0) return hipMemsetAsync(out_offsets, 0, 8, st) == hipSuccess &&
                            hipMemsetAsync(total, 0, 8, st) == hipSuccess ? RURE_AMD_OK : RURE_AMD_ERR_HIP;
