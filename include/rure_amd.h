@@ -166,7 +166,18 @@ int rure_amd_is_match_batch(rure *re, const rure_amd_batch *batch, uint8_t *out,
 /* Batched rure_shortest_match: end[i] or SIZE_MAX. */
 int rure_amd_shortest_match_batch(rure *re, const rure_amd_batch *batch, size_t *end, void *stream);
 /* Batched rure_set_matches (rure.h:532-533): bit j of mask[i] set iff
- * pattern j matches; sets of at most 64 patterns (RURE_AMD_ERR_ARG above). */
+ * pattern j matches; sets of at most 64 patterns (RURE_AMD_ERR_ARG above).
+ * This call and the next, for a set whose DFA kernels answer: they only
+ * enqueue work on `stream`, never wait for it and read nothing back.  Few
+ * long fixed-stride haystacks (256 KiB or more to search, fewer than 128 per
+ * compute unit) are scanned in parallel chunks whose patterns are ORed into
+ * the mask word, the same mask as one lane per haystack gives
+ * (rure_amd_last_set_units tells; rure_set_matches and rure_set_is_match on a
+ * long host buffer take the same scan).  That holds for a set whose DFA
+ * cannot quit and that is not anchored at the start in every pattern; sets
+ * with a Unicode word boundary, such anchored sets and every offset batch
+ * keep one lane per haystack.  Each 64-pattern group of a larger set takes
+ * the decision for itself. */
 int rure_amd_set_matches_batch(rure_set *re, const rure_amd_batch *batch, uint64_t *mask,
                                void *stream);
 /* The same for any number of patterns: `words` >= ceil(rure_set_len / 64)
@@ -417,6 +428,17 @@ int rure_amd_dfa_export(rure *re, int which, uint32_t *trans, uint8_t *eof_match
  * end of the text / reported on entering the state), start = 128 u32. */
 int rure_amd_set_dfa_export(rure_set *re, uint32_t *trans, uint64_t *eof_mask, uint64_t *now_mask,
                             uint32_t *start);
+/* Export of the set DFA built with stripped states, which the chunked scan
+ * of long haystacks walks (host only, for tests): sizes in info (may be NULL);
+ * trans, eof_mask, now_mask and start as rure_amd_set_dfa_export, strip =
+ * states u32 (the state without the `.*?` prefix threads: no match starts
+ * from there on), reach = states u64 (the patterns any walk from the state
+ * can still report).  NULL arrays are skipped (query the sizes first).
+ * RURE_AMD_ERR_DFA where the set has no such automaton: no DFA, a DFA that
+ * can quit, more than 65535 states with the stripped ones, more than 64
+ * patterns (built per group), or every pattern anchored at the start. */
+int rure_amd_set_long_dfa_export(rure_set *re, rure_amd_dfa_info *info, uint32_t *trans, uint64_t *eof_mask,
+                                 uint64_t *now_mask, uint32_t *start, uint32_t *strip, uint64_t *reach);
 /* Core form of a large set's DFA (used by the set kernel when the set DFA has
  * more than 255 ordinary or match-reporting states): sizes in info; lds =
  * 256-byte class map + (hot + 1) x K u16 entries (next core << 6 | output
@@ -606,6 +628,13 @@ uint64_t rure_amd_last_iter_units(uint64_t *haystacks);
  * writes them into a pinned host record): this call waits for the work that
  * the batched call enqueued on its stream. */
 uint64_t rure_amd_last_long_units(uint64_t *haystacks, uint64_t *chunk);
+/* Diagnostics (host only, one value for the whole process likewise): the
+ * units the last chunked RegexSet launch cut its batch into; *haystacks (may
+ * be NULL) = that batch's haystack count, *chunk (may be NULL) = the unit size
+ * in bytes.  All 0 before the first such launch and after a set call (a
+ * 64-pattern group's, for larger sets) that did not chunk.  The host knows
+ * the geometry: this call waits for nothing. */
+uint64_t rure_amd_last_set_units(uint64_t *haystacks, uint64_t *chunk);
 /* Debug-only overrides of the engine dispatch and launch geometry
  * (regex_amd/csrc/host/knobs.hpp lists them): replaces the whole override
  * table, read once per process from RURE_AMD_DEBUG, by spec

@@ -1088,6 +1088,36 @@ class RegexSet(object):
                                          start.ctypes.data), "set_dfa_export")
         return info, trans.reshape(n, 256), eof, now, start
 
+    def long_dfa_tables(self):
+        """The set DFA with stripped states that the chunked scan of long
+        haystacks walks: (info, trans (states, 256), eof_mask, now_mask,
+        start, strip, reach), or None where the set has none (a DFA that can
+        quit, every pattern anchored at the start, more than 64 patterns)."""
+        import numpy as np
+        info = N.DfaInfo()
+        if N.rure_amd_set_long_dfa_export(self._set, ctypes.byref(info), None, None, None, None, None, None) != N.OK:
+            return None
+        n = info.states
+        trans = np.zeros(n * 256, dtype=np.uint32)
+        eof = np.zeros(n, dtype=np.uint64)
+        now = np.zeros(n, dtype=np.uint64)
+        start = np.zeros(128, dtype=np.uint32)
+        strip = np.zeros(n, dtype=np.uint32)
+        reach = np.zeros(n, dtype=np.uint64)
+        _check(N.rure_amd_set_long_dfa_export(self._set, ctypes.byref(info), trans.ctypes.data, eof.ctypes.data,
+                                              now.ctypes.data, start.ctypes.data, strip.ctypes.data,
+                                              reach.ctypes.data), "set_long_dfa_export")
+        d = {k: getattr(info, k) for k, _ in N.DfaInfo._fields_}
+        return d, trans.reshape(n, 256), eof, now, start, strip, reach
+
+    @staticmethod
+    def last_long_units():
+        """(units, haystacks, chunk) of the last chunked RegexSet launch of
+        this process; (0, 0, 0) after a set call that did not chunk."""
+        n, c = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        units = N.rure_amd_last_set_units(ctypes.byref(n), ctypes.byref(c))
+        return int(units), int(n.value), int(c.value)
+
     def nfa_tables(self):
         return _nfa_export(N.rure_amd_set_nfa_export, self._set)
 

@@ -227,6 +227,10 @@ def last_long_units():
     return int(units), int(n.value), int(c.value)
 
 
+rure_amd_last_set_units = _sig("rure_amd_last_set_units", ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
+                               ctypes.POINTER(ctypes.c_uint64))
+rure_amd_set_long_dfa_export = _sig("rure_amd_set_long_dfa_export", ctypes.c_int, VP, ctypes.POINTER(DfaInfo), VP, VP,
+                                    VP, VP, VP, VP)
 rure_amd_debug_set = _sig("rure_amd_debug_set", ctypes.c_int, ctypes.c_char_p)
 rure_amd_first_byte_export = _sig("rure_amd_first_byte_export", ctypes.c_int, VP, VP)
 rure_amd_lex_export = _sig("rure_amd_lex_export", ctypes.c_int64, VP, VP, c_size, VP)

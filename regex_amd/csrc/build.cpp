@@ -887,6 +887,36 @@ bool lazy_device(const DevTables &tc) {
   return true;
 }
 
+// A packed set DFA (plain form) into an upload blob, and its descriptor over
+// the device copy.
+struct SetDfaOffsets { size_t lds, full, mask, now, start; };
+static SetDfaOffsets add_set_dfa(Blob &b, const PackedFwd &pf) {
+  SetDfaOffsets o;
+  o.lds = b.add(pf.lds.data(), pf.lds.size());
+  o.full = b.add(pf.full.data(), pf.full.size() * 2);
+  o.mask = b.add(pf.eof_mask.data(), pf.eof_mask.size() * 8);
+  o.now = b.add(pf.now_mask.data(), pf.now_mask.size() * 8);
+  o.start = b.add(pf.start.data(), 256);
+  return o;
+}
+static SetDfaDev set_dfa_dev(const uint8_t *base, const SetDfaOffsets &o, const PackedFwd &pf, const DenseDfa &fw,
+                             size_t npat) {
+  SetDfaDev s{};
+  s.lds_image = base + o.lds;
+  s.lds_bytes = (uint32_t)pf.lds.size();
+  s.hot = pf.hot;
+  s.full = (const uint16_t *)(base + o.full);
+  s.eof_mask = (const uint64_t *)(base + o.mask);
+  s.now_mask = (const uint64_t *)(base + o.now);
+  s.all = npat >= 64 ? ~0ull : ((1ull << npat) - 1);
+  s.start = (const uint16_t *)(base + o.start);
+  s.n_normal = fw.n_normal;
+  s.n_match_end = fw.n_match_end;
+  s.dead = fw.dead;
+  s.quit = fw.quit < 0 ? 0xFFFFFFFFu : (uint32_t)fw.quit;
+  return s;
+}
+
 DevTables *set_device(rure_set *rs, std::string *err) {
   if (!build_set(rs)) { if (err) *err = rs->dfa_err; return nullptr; }
   int d = 0;
@@ -900,7 +930,7 @@ DevTables *set_device(rure_set *rs, std::string *err) {
   t.cus = device_cus(d);
   NfaOffsets no{};
   if (rs->nfa_ok) no = add_nfa(b, rs->nt);
-  size_t o_lds = 0, o_full = 0, o_mask = 0, o_now = 0, o_start = 0;
+  SetDfaOffsets so{};
   size_t c_lds = 0, c_core = 0, c_out = 0, c_eof = 0, c_start = 0;
   const CoreSet &cs = rs->cores;
   if (rs->dfa_ok && cs.ok) {
@@ -911,11 +941,7 @@ DevTables *set_device(rure_set *rs, std::string *err) {
     c_start = b.add(cs.start, 256);
   }
   if (rs->dfa_ok) {
-    o_lds = b.add(pf.lds.data(), pf.lds.size());
-    o_full = b.add(pf.full.data(), pf.full.size() * 2);
-    o_mask = b.add(pf.eof_mask.data(), pf.eof_mask.size() * 8);
-    o_now = b.add(pf.now_mask.data(), pf.now_mask.size() * 8);
-    o_start = b.add(pf.start.data(), 256);
+    so = add_set_dfa(b, pf);
   }
   if (!upload_blob(b, &t, err)) return nullptr;
   uint8_t *base = (uint8_t *)t.blob;
@@ -925,18 +951,7 @@ DevTables *set_device(rure_set *rs, std::string *err) {
     const DenseDfa &fw = rs->dfa;
     t.has_dfa = true;
     t.quit_possible = fw.quit >= 0;
-    t.s.lds_image = base + o_lds;
-    t.s.lds_bytes = (uint32_t)pf.lds.size();
-    t.s.hot = pf.hot;
-    t.s.full = (const uint16_t *)(base + o_full);
-    t.s.eof_mask = (const uint64_t *)(base + o_mask);
-    t.s.now_mask = (const uint64_t *)(base + o_now);
-    t.s.all = rs->exprs.size() >= 64 ? ~0ull : ((1ull << rs->exprs.size()) - 1);
-    t.s.start = (const uint16_t *)(base + o_start);
-    t.s.n_normal = fw.n_normal;
-    t.s.n_match_end = fw.n_match_end;
-    t.s.dead = fw.dead;
-    t.s.quit = fw.quit < 0 ? 0xFFFFFFFFu : (uint32_t)fw.quit;
+    t.s = set_dfa_dev(base, so, pf, fw, rs->exprs.size());
     if (cs.ok) {
       t.use_cores = true;
       t.c.lds_image = base + c_lds;
@@ -960,6 +975,71 @@ DevTables *set_device(rure_set *rs, std::string *err) {
   }
   return &(rs->dev[d] = t);
 }
+
+// The set DFA with stripped states for the chunked scan of long haystacks
+// (set_long.hip), built on the first long call.  Not for a set without a
+// combined DFA (groups, one pattern, none materialised), a DFA that can quit
+// (the Pike VM fallback is per haystack), an automaton past the u16 tables
+// with its stripped twins, or a program anchored at the start (no `.*?`
+// prefix, so no stripped states: its lanes die where the text stops
+// matching).  reach[s]: now_mask and eof_mask over every state reachable from
+// s (s included), a fixed point over the distinct successors.
+bool build_set_long(rure_set *rs) {
+  if (rs->single || rs->exprs.size() < 2 || !rs->groups.empty() || !build_set_dfa(rs)) return false;
+  std::lock_guard<std::mutex> g(rs->mu);
+  if (rs->long_built) return rs->long_ok;
+  rs->long_built = true;
+  if (rs->dfa.quit >= 0 || rs->fwd.has_unicode_word_boundary || rs->fwd.dotstar_end == 0) return false;
+  DfaBuildLimits lim;
+  lim.strip = true;
+  std::string e;
+  DenseDfa &d = rs->ldfa;
+  if (!build_dense_dfa(rs->fwd, lim, &d, &e) || d.strip.empty() || d.quit >= 0 || !pack_forward(d, &rs->lpf, &e))
+    return false;
+  const size_t n = (size_t)d.nstates;
+  std::vector<std::vector<uint32_t>> succ(n);
+  std::vector<uint64_t> &reach = rs->lreach;
+  reach.assign(n, 0);
+  for (size_t s = 0; s < n; ++s) {
+    succ[s].assign(d.trans.begin() + s * 256, d.trans.begin() + (s + 1) * 256);
+    std::sort(succ[s].begin(), succ[s].end());
+    succ[s].erase(std::unique(succ[s].begin(), succ[s].end()), succ[s].end());
+    reach[s] = d.now_mask[s] | d.eof_mask[s];
+  }
+  for (bool changed = true; changed;) {
+    changed = false;
+    for (size_t s = n; s-- > 0;) {
+      uint64_t m = reach[s];
+      for (uint32_t t : succ[s]) m |= reach[t];
+      if (m != reach[s]) { reach[s] = m; changed = true; }
+    }
+  }
+  return rs->long_ok = true;
+}
+
+const SetLongDev *set_long_device(rure_set *rs, DevTables *t, std::string *err) {
+  if (!build_set_long(rs)) return nullptr;
+  std::lock_guard<std::mutex> g(rs->mu);
+  if (t->long_tried) return t->has_long ? &t->sl : nullptr;
+  t->long_tried = true;
+  const DenseDfa &fw = rs->ldfa;
+  std::vector<uint16_t> strip(fw.strip.size());
+  for (size_t i = 0; i < strip.size(); ++i) strip[i] = (uint16_t)fw.strip[i];
+  Blob b;
+  const SetDfaOffsets so = add_set_dfa(b, rs->lpf);
+  const size_t o_strip = b.add(strip.data(), strip.size() * 2);
+  const size_t o_reach = b.add(rs->lreach.data(), rs->lreach.size() * 8);
+  DevTables tmp;
+  if (!upload_blob(b, &tmp, err)) return nullptr;
+  const uint8_t *base = (const uint8_t *)tmp.blob;
+  t->long_blob = tmp.blob;
+  t->sl.d = set_dfa_dev(base, so, rs->lpf, fw, rs->exprs.size());
+  t->sl.strip = (const uint16_t *)(base + o_strip);
+  t->sl.reach = (const uint64_t *)(base + o_reach);
+  t->has_long = true;
+  return &t->sl;
+}
+
 
 
 // The first-byte start rule of FwdDfaDev::fb_n, decided on the find_iter DFA

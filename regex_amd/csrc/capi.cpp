@@ -383,6 +383,7 @@ void rure_set_free(rure_set *rs) {
     (void)hipSetDevice(kv.first);
     (void)hipFree(kv.second.blob);
     if (kv.second.core_blob) (void)hipFree(kv.second.core_blob);
+    if (kv.second.long_blob) (void)hipFree(kv.second.long_blob);
     (void)hipSetDevice(cur);
   }
   delete rs;
@@ -962,6 +963,22 @@ int rure_amd_set_dfa_export(rure_set *rs, uint32_t *trans, uint64_t *eof_mask, u
   return RURE_AMD_OK;
 }
 
+int rure_amd_set_long_dfa_export(rure_set *rs, rure_amd_dfa_info *info, uint32_t *trans, uint64_t *eof_mask,
+                                 uint64_t *now_mask, uint32_t *start, uint32_t *strip, uint64_t *reach) {
+  if (!rs || rs->single || rs->exprs.size() < 2) return RURE_AMD_ERR_ARG;
+  if (info) memset(info, 0, sizeof(*info));
+  if (!build_set_long(rs)) return RURE_AMD_ERR_DFA;
+  const DenseDfa &d = rs->ldfa;
+  if (info) fill_info(d, rs->fwd, rs->lpf.hot, info);
+  if (trans) memcpy(trans, d.trans.data(), d.trans.size() * 4);
+  if (eof_mask) memcpy(eof_mask, d.eof_mask.data(), d.eof_mask.size() * 8);
+  if (now_mask) memcpy(now_mask, d.now_mask.data(), d.now_mask.size() * 8);
+  if (start) memcpy(start, d.start, sizeof(d.start));
+  if (strip) memcpy(strip, d.strip.data(), d.strip.size() * 4);
+  if (reach) memcpy(reach, rs->lreach.data(), rs->lreach.size() * 8);
+  return RURE_AMD_OK;
+}
+
 int rure_amd_set_core_export(rure_set *rs, rure_amd_core_info *info, uint8_t *lds, uint16_t *gcore,
                              uint64_t *gout, uint64_t *eof, uint16_t *start) {
   if (!rs || rs->single || rs->exprs.size() < 2) return RURE_AMD_ERR_ARG;
@@ -1132,6 +1149,9 @@ int rure_amd_last_fwd_path(void) { return rure_amd::last_fwd_path(); }
 uint64_t rure_amd_last_iter_units(uint64_t *haystacks) { return rure_amd::last_iter_units(haystacks); }
 uint64_t rure_amd_last_long_units(uint64_t *haystacks, uint64_t *chunk) {
   return rure_amd::last_long_units(haystacks, chunk);
+}
+uint64_t rure_amd_last_set_units(uint64_t *haystacks, uint64_t *chunk) {
+  return rure_amd::last_set_units(haystacks, chunk);
 }
 int rure_amd_suffix_forward(rure *re) {
   if (!re) return RURE_AMD_ERR_ARG;

@@ -25,6 +25,22 @@ void note_iter_units(uint64_t units, uint64_t haystacks) {
   g_iter_units[1] = haystacks;
 }
 
+// rure_amd_last_set_units: likewise (the host knows the geometry).
+static std::mutex g_set_units_mu;
+static uint64_t g_set_units[3] = {0, 0, 0};
+uint64_t last_set_units(uint64_t *haystacks, uint64_t *chunk) {
+  std::lock_guard<std::mutex> g(g_set_units_mu);
+  if (haystacks) *haystacks = g_set_units[1];
+  if (chunk) *chunk = g_set_units[2];
+  return g_set_units[0];
+}
+void note_set_units(uint64_t units, uint64_t haystacks, uint64_t chunk) {
+  std::lock_guard<std::mutex> g(g_set_units_mu);
+  g_set_units[0] = units;
+  g_set_units[1] = haystacks;
+  g_set_units[2] = chunk;
+}
+
 // rure_amd_last_long_units: the deferred long scan's figures (haystacks,
 // chunk, units) are made on the device, so its geometry kernel writes them
 // into one pinned record of the process and each call records an event behind
@@ -452,8 +468,40 @@ static hipError_t run_regex(int mode, const BatchDev &b, const DevTables &t, voi
 }
 
 
-// exec.rs:998-1038 many_matches_at for a batch.
-static hipError_t run_set(const BatchDev &b, const DevTables &t, uint64_t *out, hipStream_t st, int dfa_grid) {
+// Few long fixed-stride haystacks of a RegexSet: one lane per haystack would
+// walk a 1 GiB log alone, so the scan is cut into units (launch_set_long) of
+// the long scan's size, long_batch's threshold and chunk rule.  Needs the
+// strip-built set automaton (set_long_device: not a DFA that can quit, nor a
+// set anchored at the start), which is built here on the first such call.
+// Offset batches keep one lane per haystack.  Knobs set_long: 0 never, 2 at
+// any length and count (tests); set_chunk: the unit size in bytes.
+static const SetLongDev *set_long_batch(rure_set *rs, const BatchDev &b, DevTables *t, uint64_t *chunk) {
+  const long long mode = knob(Knob::SetLong);
+  if (mode == 0 || b.offs || b.count == 0 || !t->has_dfa || t->quit_possible) return nullptr;
+  const uint64_t span = b.length > b.start ? b.length - b.start : 0;
+  if (mode != 2 && (span < kLongSpan || b.count >= (uint64_t)t->cus * 128)) return nullptr;
+  std::string err;
+  const SetLongDev *sl = set_long_device(rs, t, &err);
+  if (!sl) return nullptr;
+  *chunk = unit_bytes(span, b.count, lanes_in_flight(t->cus, Knob::LongLanes), kLongFloor);
+  if (knob(Knob::SetChunk) > 0) *chunk = std::max<uint64_t>(16, knob(Knob::SetChunk));
+  return sl;
+}
+
+// exec.rs:998-1038 many_matches_at for a batch.  sl: the chunked scan's
+// automaton where set_long_batch chose it (chunk its unit), else null.
+static hipError_t run_set(const BatchDev &b, const DevTables &t, uint64_t *out, hipStream_t st, int dfa_grid,
+                          const SetLongDev *sl, uint64_t chunk) {
+  if (sl) {
+    uint64_t units = 0;
+    const hipError_t e = launch_set_long(b, *sl, chunk, out, st, t.cus, &units);
+    if (e == hipSuccess) {
+      note_fwd_path(RURE_AMD_PATH_LONG_SCAN);
+      note_set_units(units, b.count, chunk);
+    }
+    return e;
+  }
+  note_set_units(0, 0, 0);
   if (!t.has_dfa) return run_pike(MODE_SET, false, b, t, out, st);
   const auto step = [&](const BatchDev &bq) {
     return t.use_cores ? launch_set_cores(bq, t.c, out, st, t.cus) : launch_dfa_set(bq, t.s, out, st, dfa_grid);
@@ -569,6 +617,9 @@ uint64_t set_single_call(rure_set *rs, const uint8_t *hay, size_t len, size_t st
   std::string err;
   DevTables *t = set_device(rs, &err);
   if (!t) die(err);
+  uint64_t chunk = 0;
+  BatchDev probe{nullptr, nullptr, 0, len, 1, start};
+  const SetLongDev *sl = set_long_batch(rs, probe, t, &chunk);  // locks rs->mu
   std::lock_guard<std::mutex> g(rs->mu);
   int d = 0;
   if (!hip_ok(hipGetDevice(&d), &err)) die(err);
@@ -576,7 +627,7 @@ uint64_t set_single_call(rure_set *rs, const uint8_t *hay, size_t len, size_t st
   hipStream_t st = rs->stage.stream;
   if (len && !hip_ok(hipMemcpyAsync(rs->stage.hay, hay, len, hipMemcpyHostToDevice, st), &err)) die(err);
   BatchDev b{rs->stage.hay, nullptr, 0, len, 1, start};
-  if (!hip_ok(run_set(b, *t, rs->stage.res, st, 1), &err)) die(err);
+  if (!hip_ok(run_set(b, *t, rs->stage.res, st, 1, sl, chunk), &err)) die(err);
   uint64_t out = 0;
   if (!hip_ok(hipMemcpyAsync(&out, rs->stage.res, 8, hipMemcpyDeviceToHost, st), &err)) die(err);
   if (!hip_ok(hipStreamSynchronize(st), &err)) die(err);
@@ -641,9 +692,11 @@ int set_batch_word(rure_set *rs, const BatchDev &b, uint64_t *mask, hipStream_t 
   std::string err;
   DevTables *t = set_device(rs, &err);
   if (!t) return err.rfind("HIP", 0) == 0 ? RURE_AMD_ERR_HIP : RURE_AMD_ERR_DFA;
-  if (t->use_cores && !t->cores_adapted && !adapt_cores(rs, t, b, stream, &err)) return RURE_AMD_ERR_HIP;
+  uint64_t chunk = 0;
+  const SetLongDev *sl = set_long_batch(rs, b, t, &chunk);
+  if (!sl && t->use_cores && !t->cores_adapted && !adapt_cores(rs, t, b, stream, &err)) return RURE_AMD_ERR_HIP;
   int grid = grid_for(b.count, t->s.lds_bytes, t->cus);
-  if (run_set(b, *t, mask, stream, grid) != hipSuccess) return RURE_AMD_ERR_HIP;
+  if (run_set(b, *t, mask, stream, grid, sl, chunk) != hipSuccess) return RURE_AMD_ERR_HIP;
   return RURE_AMD_OK;
 }
 

@@ -49,6 +49,8 @@ enum class Knob : int {
   LongRagged,      // 0: offset batches of find / is_match / shortest_match one lane per haystack; 2: defer any haystack longer than a chunk
   LongChunk,       // the chunk floor in bytes of that deferred long scan (no odd-lines rounding)
   LongList,        // the capacity of its list of deferred haystacks
+  SetLong,         // 0: a RegexSet's long haystacks one lane each; 2: chunked at any length and count
+  SetChunk,        // the unit size in bytes of the chunked RegexSet scan (floor 16)
   kCount
 };
 

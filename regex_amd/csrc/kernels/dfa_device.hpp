@@ -115,6 +115,33 @@ __device__ __forceinline__ uint32_t fast4(uint32_t s, uint32_t w, const uint8_t 
   return s;
 }
 
+// One byte of a set DFA (dfa_set_kernel, set_long_kernel): the hot rows in
+// LDS, else the full table, where the patterns reported on entering a state
+// are ORed into mask.  True: the walk is over (dead, quit, or every pattern
+// matched: nothing left to learn).
+__device__ __forceinline__ bool set_careful(uint32_t &s, uint64_t &mask, const SetDfaDev &f, uint32_t b,
+                                            bool &quit) {
+  s = f.full[(size_t)s * 256 + b];
+  if (s >= f.n_normal) {
+    if (s < f.n_match_end) {
+      mask |= f.now_mask[s];
+      return mask == f.all;  // every pattern matched: nothing left to learn
+    }
+    if (s == f.quit) quit = true;
+    return true;  // dead or quit
+  }
+  return false;
+}
+
+__device__ __forceinline__ bool set_step1(uint32_t &s, uint64_t &mask, const SetDfaDev &f, const uint8_t *lds,
+                                          uint32_t b, bool &quit) {
+  if (s < f.hot) {
+    uint32_t t = lds[__umul24(s, kRow) + b];
+    if (t != f.hot) { s = t; return false; }
+  }
+  return set_careful(s, mask, f, b, quit);
+}
+
 // 4 exact steps (every state in LDS); mx collects the largest state entered
 // (off the dependency chain): mx < n_normal means no match / dead / quit.
 __device__ __forceinline__ uint32_t exact4(uint32_t s, uint32_t w, const uint8_t *lds, uint32_t &mx) {

@@ -395,30 +395,7 @@ __global__ __launch_bounds__(256) void dfa_fwd_tile_kernel(BatchDev bt, FwdDfaDe
 // state (dfa.rs:1004-1015); our set DFA reports the patterns reached by each
 // step instead (now_mask of the state entered, host/dfa_build.cpp), so the
 // lane ORs them up: same union, far fewer states.  Only the few states that
-// report matches leave the LDS fast path.
-__device__ __forceinline__ bool set_careful(uint32_t &s, uint64_t &mask, const SetDfaDev &f, uint32_t b,
-                                            bool &quit) {
-  s = f.full[(size_t)s * 256 + b];
-  if (s >= f.n_normal) {
-    if (s < f.n_match_end) {
-      mask |= f.now_mask[s];
-      return mask == f.all;  // every pattern matched: nothing left to learn
-    }
-    if (s == f.quit) quit = true;
-    return true;  // dead or quit
-  }
-  return false;
-}
-
-__device__ __forceinline__ bool set_step1(uint32_t &s, uint64_t &mask, const SetDfaDev &f, const uint8_t *lds,
-                                          uint32_t b, bool &quit) {
-  if (s < f.hot) {
-    uint32_t t = lds[__umul24(s, kRow) + b];
-    if (t != f.hot) { s = t; return false; }
-  }
-  return set_careful(s, mask, f, b, quit);
-}
-
+// report matches leave the LDS fast path (set_step1, dfa_device.hpp).
 template <bool STRIDED>
 __global__ __launch_bounds__(256) void dfa_set_kernel(BatchDev bt, SetDfaDev f, uint64_t *out) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];

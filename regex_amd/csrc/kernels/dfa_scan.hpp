@@ -241,6 +241,16 @@ struct SetDfaDev {
   uint32_t n_normal, n_match_end, dead, quit;
 };
 
+// The set DFA built with stripped states, for the chunked scan of long
+// haystacks (set_long.hip): strip[s] = s without the `.*?` prefix threads (no
+// match starts from there on), reach[s] = the patterns any walk from s can
+// still report (now_mask and eof_mask over every state reachable from s).
+struct SetLongDev {
+  SetDfaDev d;
+  const uint16_t *strip;
+  const uint64_t *reach;
+};
+
 // Set DFA in "core" form for large sets (host: build_set_cores): states that
 // differ only in the matches their entry reports share a core; a transition
 // (core, byte class) carries the next core and an output code.  Entries of
@@ -550,6 +560,10 @@ void note_fwd_path(rure_amd_path path);
 // process (rure_amd_last_iter_units; 0, 0 before the first).
 uint64_t last_iter_units(uint64_t *haystacks);
 void note_iter_units(uint64_t units, uint64_t haystacks);
+// The units, haystacks and unit size of the last chunked RegexSet launch
+// (rure_amd_last_set_units; all 0 after a set call that did not chunk).
+uint64_t last_set_units(uint64_t *haystacks, uint64_t *chunk);
+void note_set_units(uint64_t units, uint64_t haystacks, uint64_t chunk);
 // Kernel timer (rure_amd_kernel_timer): HIP event pairs around bracketed launches.
 void ktimer_begin(hipStream_t st);
 void ktimer_end(hipStream_t st);
@@ -572,6 +586,11 @@ hipError_t launch_mask_column(const uint8_t *s8, const uint64_t *s64, uint64_t n
 hipError_t launch_dfa_anchored_rev(int mode, const BatchDev &b, const RevDfaDev &r, void *out, hipStream_t st,
                                    int grid);
 hipError_t launch_dfa_set(const BatchDev &b, const SetDfaDev &f, uint64_t *out, hipStream_t st, int grid);
+// RegexSet masks over few long fixed-stride haystacks, chunked (set_long.hip):
+// out[h] is zeroed on the stream and the units OR their patterns into it.
+// *units = the units the batch was cut into.
+hipError_t launch_set_long(const BatchDev &b, const SetLongDev &f, uint64_t chunk, uint64_t *out, hipStream_t st,
+                           int cus, uint64_t *units);
 
 // An automaton past the u16 tables (more than 65535 states, host
 // kBigDfaRawStates budget): u32 next states in column form, trans[s * ncol +

@@ -92,6 +92,11 @@ struct DevTables {
   void *lazy_buf = nullptr, *lazy_rblob = nullptr;
   size_t lazy_cap = 0;
   RevDfaDev lr{};
+  // sets: the strip-built automaton of the chunked long scan (set_long_device),
+  // uploaded on the first long call
+  bool long_tried = false, has_long = false;
+  void *long_blob = nullptr;
+  SetLongDev sl{};
   bool quit_possible = false;  // the DFA can quit (Unicode \b): Pike VM fallback pass
   bool anchored_rev = false;   // MatchType::DfaAnchoredReverse (exec.rs:1175-1177)
   // The reference's match type where its searches differ from a forward DFA
@@ -282,6 +287,12 @@ struct rure_set {
   DenseDfa dfa;
   PackedFwd pf;
   CoreSet cores;      // core form, used when the hot table cannot hold the set DFA
+  // the set DFA with dotstar-stripped states, for the chunked scan of long
+  // haystacks (build_set_long; built on the first long call)
+  bool long_built = false, long_ok = false;
+  DenseDfa ldfa;
+  PackedFwd lpf;
+  std::vector<uint64_t> lreach;  // per state: the patterns any walk from it can still report
   NfaTables nt;
   bool nfa_ok = false;
   std::map<int, DevTables> dev;
@@ -341,6 +352,8 @@ DevTables *regex_device(rure *re, std::string *err);
 bool big_device(const DevTables &tc);
 bool lazy_device(const DevTables &tc);
 DevTables *set_device(rure_set *rs, std::string *err);
+bool build_set_long(rure_set *rs);
+const SetLongDev *set_long_device(rure_set *rs, DevTables *t, std::string *err);
 uint32_t first_byte_rule(const DenseDfa &d, uint32_t ustart1, bool nonempty, uint8_t bytes[4], bool *holds);
 bool run_class(const DenseDfa &d, uint32_t ustart1, bool nonempty, uint8_t cls[256], bool ascii);
 bool build_lex4(const std::vector<uint8_t> &img, uint32_t s0, std::vector<uint8_t> *out, uint32_t *s0_row);
