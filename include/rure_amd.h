@@ -176,8 +176,13 @@ int rure_amd_shortest_match_batch(rure *re, const rure_amd_batch *batch, size_t 
  * long host buffer take the same scan).  That holds for a set whose DFA
  * cannot quit and that is not anchored at the start in every pattern; sets
  * with a Unicode word boundary, such anchored sets and every offset batch
- * keep one lane per haystack.  Each 64-pattern group of a larger set takes
- * the decision for itself. */
+ * keep one lane per haystack.  A set whose automaton is past the eager state
+ * budget (no DFA; no Unicode word boundary) answers batches that fill the
+ * device from its on-demand DFA: rows are built on the host as the text
+ * needs them, so such a call synchronises `stream` between rounds, and the
+ * first call on new text pays the construction (smaller batches, and a spent
+ * memory budget, keep the Pike VM).  Each 64-pattern group of a larger set
+ * takes these decisions for itself. */
 int rure_amd_set_matches_batch(rure_set *re, const rure_amd_batch *batch, uint64_t *mask,
                                void *stream);
 /* The same for any number of patterns: `words` >= ceil(rure_set_len / 64)
@@ -439,6 +444,29 @@ int rure_amd_set_dfa_export(rure_set *re, uint32_t *trans, uint64_t *eof_mask, u
  * patterns (built per group), or every pattern anchored at the start. */
 int rure_amd_set_long_dfa_export(rure_set *re, rure_amd_dfa_info *info, uint32_t *trans, uint64_t *eof_mask,
                                  uint64_t *now_mask, uint32_t *start, uint32_t *strip, uint64_t *reach);
+/* A set's on-demand DFA as it stands (host only, for tests): the automaton
+ * that answers the batches of a set without an eager DFA, rows built as
+ * batches (or rure_amd_set_lazy_build) need them.  Sizes in info (may be
+ * NULL): states interned, columns, rows built, rows the kernel holds in LDS,
+ * and of the last batched call that took it the rounds it ran and 1 if it
+ * gave up (memory budget, too many rounds) and the Pike VM answered.  trans =
+ * states x columns entries (next state, | 0x80000000 when entering it
+ * reports matches; 0 = dead; 0x7FFFFFFF = the row is not built yet), now /
+ * eof_mask = states u64 (patterns reported on entering the state / at the
+ * end of the text from it), built = states bytes, start = 128 entries by
+ * start-flag index, colmap = 256 bytes (byte -> column).  NULL arrays are
+ * skipped (query the sizes first; they grow with every row built).
+ * RURE_AMD_ERR_DFA where the set gets no such automaton: a member with a
+ * Unicode word boundary, more than 64 patterns (searched per group). */
+typedef struct rure_amd_lazy_info {
+  uint32_t states, columns, rows_built, hot_rows, rounds, fell_back;
+} rure_amd_lazy_info;
+int rure_amd_set_lazy_export(rure_set *re, rure_amd_lazy_info *info, uint32_t *trans, uint64_t *now,
+                             uint64_t *eof_mask, uint8_t *built, uint32_t *start, uint8_t *colmap);
+/* Builds the rows of the n named states of that automaton, then `ahead` more
+ * in discovery order: what one round of a batched call does between two
+ * launches.  Returns 1, 0 when the memory budget is spent, or an error. */
+int rure_amd_set_lazy_build(rure_set *re, const uint32_t *states, size_t n, size_t ahead);
 /* Core form of a large set's DFA (used by the set kernel when the set DFA has
  * more than 255 ordinary or match-reporting states): sizes in info; lds =
  * 256-byte class map + (hot + 1) x K u16 entries (next core << 6 | output
@@ -591,7 +619,7 @@ typedef enum rure_amd_path {
   RURE_AMD_PATH_BIG_DFA = -6,           /* the big (u32) DFA */
   RURE_AMD_PATH_LINES = -8,             /* the ragged line kernel */
   RURE_AMD_PATH_SUFFIX_LONG = -9,       /* the chunked DfaSuffix scan */
-  RURE_AMD_PATH_LAZY_DFA = -10,         /* the on-demand DFA */
+  RURE_AMD_PATH_LAZY_DFA = -10,         /* the on-demand DFA (a regex's, or a set's) */
   RURE_AMD_PATH_SUFFIX_ITER = -11,      /* the DfaSuffix find_iter */
   RURE_AMD_PATH_ITER_LOOKS = -12,       /* the chunked find_iter of a look-around regex answered */
   RURE_AMD_PATH_ITER_LOOKS_QUIT = -13,  /* it quit: one haystack per wavefront answers */

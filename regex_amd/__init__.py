@@ -1110,6 +1110,41 @@ class RegexSet(object):
         d = {k: getattr(info, k) for k, _ in N.DfaInfo._fields_}
         return d, trans.reshape(n, 256), eof, now, start, strip, reach
 
+    def lazy_tables(self):
+        """The set's on-demand DFA as it stands: (info, trans (states,
+        columns), now, eof_mask, built, start, colmap); entries are next
+        state | 0x80000000 when entering it reports matches, 0 = dead,
+        0x7FFFFFFF = the row is not built yet.  info: states, columns,
+        rows_built, hot_rows, and rounds / fell_back of the last batched call
+        that took it.  Raises RuntimeError where the set gets no such automaton (a
+        Unicode word boundary, more than 64 patterns)."""
+        import numpy as np
+        info = N.LazyInfo()
+        _check(N.rure_amd_set_lazy_export(self._set, ctypes.byref(info), None, None, None, None, None, None),
+               "set_lazy_export")
+        n, k = info.states, info.columns
+        trans = np.zeros(n * k, dtype=np.uint32)
+        now = np.zeros(n, dtype=np.uint64)
+        eof = np.zeros(n, dtype=np.uint64)
+        built = np.zeros(n, dtype=np.uint8)
+        start = np.zeros(128, dtype=np.uint32)
+        colmap = np.zeros(256, dtype=np.uint8)
+        _check(N.rure_amd_set_lazy_export(self._set, ctypes.byref(info), trans.ctypes.data, now.ctypes.data,
+                                          eof.ctypes.data, built.ctypes.data, start.ctypes.data, colmap.ctypes.data),
+               "set_lazy_export")
+        d = {f: getattr(info, f) for f, _ in N.LazyInfo._fields_}
+        return d, trans.reshape(n, k), now, eof, built, start, colmap
+
+    def lazy_build(self, states, ahead=0):
+        """Builds the rows of `states` of the on-demand DFA, then `ahead` more
+        in discovery order (one round's host work); False once the memory
+        budget is spent."""
+        arr = (ctypes.c_uint32 * max(len(states), 1))(*[int(s) for s in states])
+        rc = N.rure_amd_set_lazy_build(self._set, arr, len(states), ahead)
+        if rc < 0:
+            _check(rc, "set_lazy_build")
+        return rc == 1
+
     @staticmethod
     def last_long_units():
         """(units, haystacks, chunk) of the last chunked RegexSet launch of

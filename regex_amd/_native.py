@@ -231,6 +231,13 @@ rure_amd_last_set_units = _sig("rure_amd_last_set_units", ctypes.c_uint64, ctype
                                ctypes.POINTER(ctypes.c_uint64))
 rure_amd_set_long_dfa_export = _sig("rure_amd_set_long_dfa_export", ctypes.c_int, VP, ctypes.POINTER(DfaInfo), VP, VP,
                                     VP, VP, VP, VP)
+class LazyInfo(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint32) for k in ("states", "columns", "rows_built", "hot_rows", "rounds", "fell_back")]
+
+
+rure_amd_set_lazy_export = _sig("rure_amd_set_lazy_export", ctypes.c_int, VP, ctypes.POINTER(LazyInfo), VP, VP, VP,
+                                VP, VP, VP)
+rure_amd_set_lazy_build = _sig("rure_amd_set_lazy_build", ctypes.c_int, VP, VP, c_size, c_size)
 rure_amd_debug_set = _sig("rure_amd_debug_set", ctypes.c_int, ctypes.c_char_p)
 rure_amd_first_byte_export = _sig("rure_amd_first_byte_export", ctypes.c_int, VP, VP)
 rure_amd_lex_export = _sig("rure_amd_lex_export", ctypes.c_int64, VP, VP, c_size, VP)

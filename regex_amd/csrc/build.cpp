@@ -1017,6 +1017,25 @@ bool build_set_long(rure_set *rs) {
   return rs->long_ok = true;
 }
 
+// A set's on-demand DFA (host LazyDfa over the set program; big_dfa.hip
+// lazy_set_kernel), created on the first batch that needs it.  Not for a set
+// with a Unicode word boundary (the on-demand automaton has no quit state:
+// the Pike VM keeps it, as for a regex), nor for more than 64 patterns (one
+// mask word; each 64-pattern group of a larger set is such a set itself).
+// Sets get no eager u32 tier: past the u16 budget the states a batch visits
+// are built on demand within kBigDfaBytes (knob big_bytes).
+LazyDfa *set_lazy(rure_set *rs) {
+  if (!rs || rs->single || rs->exprs.size() < 2 || rs->exprs.size() > 64 || !rs->groups.empty()) return nullptr;
+  std::lock_guard<std::mutex> g(rs->mu);
+  if (rs->lazy_tried) return rs->lazy.get();
+  rs->lazy_tried = true;
+  if (rs->fwd.has_unicode_word_boundary) return nullptr;
+  size_t budget = kBigDfaBytes;
+  if (knob(Knob::BigBytes) > 0) budget = (size_t)knob(Knob::BigBytes);
+  rs->lazy.reset(new LazyDfa(rs->fwd, budget));
+  return rs->lazy.get();
+}
+
 const SetLongDev *set_long_device(rure_set *rs, DevTables *t, std::string *err) {
   if (!build_set_long(rs)) return nullptr;
   std::lock_guard<std::mutex> g(rs->mu);

@@ -384,6 +384,7 @@ void rure_set_free(rure_set *rs) {
     (void)hipFree(kv.second.blob);
     if (kv.second.core_blob) (void)hipFree(kv.second.core_blob);
     if (kv.second.long_blob) (void)hipFree(kv.second.long_blob);
+    if (kv.second.lazy_buf) (void)hipFree(kv.second.lazy_buf);
     (void)hipSetDevice(cur);
   }
   delete rs;
@@ -977,6 +978,38 @@ int rure_amd_set_long_dfa_export(rure_set *rs, rure_amd_dfa_info *info, uint32_t
   if (strip) memcpy(strip, d.strip.data(), d.strip.size() * 4);
   if (reach) memcpy(reach, rs->lreach.data(), rs->lreach.size() * 8);
   return RURE_AMD_OK;
+}
+
+int rure_amd_set_lazy_export(rure_set *rs, rure_amd_lazy_info *info, uint32_t *trans, uint64_t *now,
+                             uint64_t *eof_mask, uint8_t *built, uint32_t *start, uint8_t *colmap) {
+  if (!rs || rs->single || rs->exprs.size() < 2) return RURE_AMD_ERR_ARG;
+  if (info) memset(info, 0, sizeof(*info));
+  LazyDfa *L = set_lazy(rs);
+  if (!L) return RURE_AMD_ERR_DFA;
+  std::lock_guard<std::mutex> g(rs->mu);
+  if (info)
+    *info = rure_amd_lazy_info{L->nstates(), L->ncol, (uint32_t)L->nbuilt(),
+                               std::min<uint32_t>(L->nstates(), lazy_dfa_hot_rows(L->ncol)), rs->lazy_rounds,
+                               rs->lazy_fell_back};
+  if (trans) memcpy(trans, L->trans.data(), L->trans.size() * 4);
+  if (now) memcpy(now, L->now.data(), L->now.size() * 8);
+  if (eof_mask) memcpy(eof_mask, L->eof_mask.data(), L->eof_mask.size() * 8);
+  if (built) memcpy(built, L->built.data(), L->built.size());
+  if (start) memcpy(start, L->start, sizeof(L->start));
+  if (colmap) memcpy(colmap, L->colmap, 256);
+  return RURE_AMD_OK;
+}
+
+int rure_amd_set_lazy_build(rure_set *rs, const uint32_t *states, size_t n, size_t ahead) {
+  if (!rs || rs->single || rs->exprs.size() < 2 || (!states && n)) return RURE_AMD_ERR_ARG;
+  LazyDfa *L = set_lazy(rs);
+  if (!L) return RURE_AMD_ERR_DFA;
+  std::lock_guard<std::mutex> g(rs->mu);
+  for (size_t i = 0; i < n; ++i) {
+    if (states[i] >= L->nstates()) return RURE_AMD_ERR_ARG;
+    if (!L->build_row(states[i])) return 0;
+  }
+  return L->expand(ahead) ? 1 : 0;
 }
 
 int rure_amd_set_core_export(rure_set *rs, rure_amd_core_info *info, uint8_t *lds, uint16_t *gcore,

@@ -294,26 +294,30 @@ static bool big_batch(const BatchDev &b, const DevTables &t) {
   return b.count >= (uint64_t)t.cus * 64;
 }
 
-// find / is_match / shortest on the on-demand forward DFA (lazy_device):
-// rounds of lazy_dfa_kernel; between rounds the host builds the rows the
-// parked lanes need (and, ahead of them, more rows in discovery order) and
-// uploads the grown table.  Synchronous, as the reference's construction
-// happens inside its search.  The reference gives up on its lazy DFA when
-// the cache thrashes (dfa.rs:1282-1293) and runs the Pike VM; here a spent
-// memory budget or kLazyRounds rounds do the same for the batch.
+// The rounds of a batched scan on an on-demand DFA (a regex's: run_lazy; a
+// set's: run_lazy_set): `launch` runs one round of the kernel; between
+// rounds the host builds the rows the parked lanes need (and, ahead of them,
+// more rows in discovery order) and uploads the grown table, which stays in
+// t.lazy_buf for the next call.  Synchronous, as the reference's
+// construction happens inside its search.  The reference gives up on its
+// lazy DFA when the cache thrashes (dfa.rs:1282-1293) and runs the Pike VM;
+// here a spent memory budget or kLazyRounds rounds do the same for the batch:
+// *ok is then false and the caller runs the Pike VM over the whole batch
+// (the rounds' scratch is freed by then).  *rounds = the rounds launched.
+// The caller holds the lock of L's owner.
 constexpr int kLazyRounds = 256;
-static hipError_t run_lazy(int mode, const BatchDev &b, const DevTables &tc, void *out, hipStream_t st) {
-  DevTables &t = const_cast<DevTables &>(tc);
-  rure *re = t.owner;
-  std::lock_guard<std::mutex> g(re->mu);
-  LazyDfa &L = *re->lazy;
+template <class Launch>
+static hipError_t lazy_rounds(LazyDfa &L, DevTables &t, uint64_t count, hipStream_t st, bool *ok_out, uint32_t *rounds,
+                              Launch launch) {
   size_t ahead = 4096;  // rows built ahead per round (knob lazy_rows: tests)
   if (knob(Knob::LazyRows) > 0) ahead = (size_t)knob(Knob::LazyRows);
   bool ok = L.nbuilt() > 0 || L.expand(ahead);
+  *ok_out = ok;
+  *rounds = 0;
   hipError_t e = hipSuccess;
   Scratch<LazyPark> pk[2];
   Scratch<unsigned long long> cnt;
-  const size_t pbytes = std::max<uint64_t>(b.count, 1) * sizeof(LazyPark);
+  const size_t pbytes = std::max<uint64_t>(count, 1) * sizeof(LazyPark);
   if ((e = pk[0].alloc(pbytes, st)) != hipSuccess) return e;
   if ((e = pk[1].alloc(pbytes, st)) != hipSuccess) return e;
   if ((e = cnt.alloc(16, st)) != hipSuccess) return e;
@@ -321,33 +325,49 @@ static hipError_t run_lazy(int mode, const BatchDev &b, const DevTables &tc, voi
   uint64_t nin = 0;
   std::vector<LazyPark> host;
   for (int round = 0; ok && e == hipSuccess; ++round) {
-    // the table: [colmap 256][start 512][eof cap][trans cap * ncol * 4]
-    const size_t ns = L.nstates(), need = 768 + ns + ns * (size_t)L.ncol * 4 + 16;
+    // the table: [colmap 256][start 512][now cap * 8][eof_mask cap * 8][eof cap][trans cap * ncol * 4]
+    // (now and eof_mask: a set's, 8-byte aligned; none for a regex)
+    const size_t ns = L.nstates(), nm = L.is_set ? ns : 0;
+    const size_t need = 768 + nm * 16 + ns + ns * (size_t)L.ncol * 4 + 16;
     if (need > t.lazy_cap) {
       if ((e = hipStreamSynchronize(st)) != hipSuccess) break;
       if (t.lazy_buf) (void)hipFree(t.lazy_buf);
       t.lazy_buf = nullptr;
+      t.lazy_up_states = 0;
       t.lazy_cap = std::max(need * 3 / 2, (size_t)1 << 20);
       if ((e = hipMalloc(&t.lazy_buf, t.lazy_cap)) != hipSuccess) { t.lazy_cap = 0; break; }
     }
     uint8_t *base = (uint8_t *)t.lazy_buf;
-    const size_t o_eof = 768, o_trans = (768 + ns + 15) & ~(size_t)15;
-    if ((e = hipMemcpyAsync(base, L.colmap, 256, hipMemcpyHostToDevice, st)) != hipSuccess) break;
-    if ((e = hipMemcpyAsync(base + 256, L.start, 512, hipMemcpyHostToDevice, st)) != hipSuccess) break;
-    if ((e = hipMemcpyAsync(base + o_eof, L.eof.data(), ns, hipMemcpyHostToDevice, st)) != hipSuccess) break;
-    if ((e = hipMemcpyAsync(base + o_trans, L.trans.data(), L.trans.size() * 4, hipMemcpyHostToDevice, st)) !=
-        hipSuccess)
-      break;
+    const size_t o_now = 768, o_mask = o_now + nm * 8, o_eof = o_mask + nm * 8, o_trans = (o_eof + ns + 15) & ~(size_t)15;
+    // Uploaded unless the device copy is this very table: states and rows
+    // only ever grow, so their counts name its contents.  A call over text
+    // whose rows exist copies nothing (1.4 M states are 186 MB).
+    if (t.lazy_up_states != ns || t.lazy_up_built != L.nbuilt()) {
+      t.lazy_up_states = 0;
+      const auto up = [&](size_t off, const void *src, size_t bytes) {
+        return bytes ? hipMemcpyAsync(base + off, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
+      };
+      if ((e = up(0, L.colmap, 256)) != hipSuccess || (e = up(256, L.start, 512)) != hipSuccess ||
+          (e = up(o_now, L.now.data(), nm * 8)) != hipSuccess ||
+          (e = up(o_mask, L.eof_mask.data(), nm * 8)) != hipSuccess || (e = up(o_eof, L.eof.data(), ns)) != hipSuccess ||
+          (e = up(o_trans, L.trans.data(), L.trans.size() * 4)) != hipSuccess)
+        break;
+      t.lazy_up_states = ns;
+      t.lazy_up_built = L.nbuilt();
+    }
     LazyDfaDev f{};
     f.colmap = base;
     f.start = (const uint32_t *)(base + 256);
+    f.now = nm ? (const uint64_t *)(base + o_now) : nullptr;
+    f.eof_mask = nm ? (const uint64_t *)(base + o_mask) : nullptr;
     f.eof = base + o_eof;
     f.trans = (const uint32_t *)(base + o_trans);
     f.ncol = L.ncol;
     f.hot = std::min<uint32_t>((uint32_t)ns, lazy_dfa_hot_rows(L.ncol));
     LazyPark *po = pk[round & 1].get();
     if ((e = hipMemsetAsync(cnt.get(), 0, 8, st)) != hipSuccess) break;
-    if ((e = launch_lazy_dfa(mode, b, f, t.lr, in, nin, po, cnt.get(), out, st, t.cus)) != hipSuccess) break;
+    if ((e = launch(f, in, nin, po, cnt.get())) != hipSuccess) break;
+    *rounds = (uint32_t)round + 1;
     unsigned long long n = 0;
     if ((e = hipMemcpyAsync(&n, cnt.get(), 8, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
     if ((e = hipStreamSynchronize(st)) != hipSuccess) break;
@@ -366,8 +386,25 @@ static hipError_t run_lazy(int mode, const BatchDev &b, const DevTables &tc, voi
     in = po;
     nin = n;
   }
+  if (e != hipSuccess) t.lazy_up_states = 0;  // (a copy may not have happened)
+  *ok_out = ok;
+  return e;
+}
+
+// find / is_match / shortest on the on-demand forward DFA (lazy_device):
+// rounds of lazy_dfa_kernel.
+static hipError_t run_lazy(int mode, const BatchDev &b, const DevTables &tc, void *out, hipStream_t st) {
+  DevTables &t = const_cast<DevTables &>(tc);
+  rure *re = t.owner;
+  std::lock_guard<std::mutex> g(re->mu);
+  bool ok = true;
+  uint32_t rounds = 0;
+  const hipError_t e = lazy_rounds(*re->lazy, t, b.count, st, &ok, &rounds,
+                                   [&](const LazyDfaDev &f, const LazyPark *in, uint64_t nin, LazyPark *po,
+                                       unsigned long long *cnt) {
+                                     return launch_lazy_dfa(mode, b, f, t.lr, in, nin, po, cnt, out, st, t.cus);
+                                   });
   if (e != hipSuccess || ok) return e;
-  pk[0].reset(), pk[1].reset(), cnt.reset();  // before the Pike VM's scratch
   return run_pike(mode, false, b, t, out, st);  // the whole batch again
 }
 
@@ -488,10 +525,40 @@ static const SetLongDev *set_long_batch(rure_set *rs, const BatchDev &b, DevTabl
   return sl;
 }
 
+// A set's matches on its on-demand DFA (set_lazy): rounds of lazy_set_kernel.
+static hipError_t run_lazy_set(rure_set *rs, const BatchDev &b, const DevTables &tc, uint64_t *out, hipStream_t st) {
+  DevTables &t = const_cast<DevTables &>(tc);  // the set's own entry of rure_set::dev
+  std::lock_guard<std::mutex> g(rs->mu);
+  const size_t np = rs->exprs.size();
+  const uint64_t all = np >= 64 ? ~0ull : (1ull << np) - 1;
+  bool ok = true;
+  const hipError_t e = lazy_rounds(*rs->lazy, t, b.count, st, &ok, &rs->lazy_rounds,
+                                   [&](const LazyDfaDev &f, const LazyPark *in, uint64_t nin, LazyPark *po,
+                                       unsigned long long *cnt) {
+                                     return launch_lazy_set(b, f, all, in, nin, po, cnt, out, st, t.cus);
+                                   });
+  rs->lazy_fell_back = e == hipSuccess && !ok;
+  if (e != hipSuccess || ok) return e;
+  return run_pike(MODE_SET, false, b, t, out, st);  // the whole batch again
+}
+
+// The on-demand DFA for a set past the eager budget, on batches that fill
+// the device: the regex rule (lazy_batch).  Knob lazy: 0 never, 1 any set
+// that can have it, also one with an eager DFA (tests); big: 2 any batch, 0
+// keeps the Pike VM.  rs is null for the single-haystack host calls, which
+// keep the Pike VM.
+static bool lazy_set_batch(rure_set *rs, const BatchDev &b, const DevTables &t) {
+  if (!rs || !rs->nfa_ok || knob(Knob::Lazy) == 0) return false;
+  const bool force = knob(Knob::Lazy) == 1;
+  if (!force && (t.has_dfa || !big_batch(b, t))) return false;
+  return set_lazy(rs) != nullptr;
+}
+
 // exec.rs:998-1038 many_matches_at for a batch.  sl: the chunked scan's
-// automaton where set_long_batch chose it (chunk its unit), else null.
-static hipError_t run_set(const BatchDev &b, const DevTables &t, uint64_t *out, hipStream_t st, int dfa_grid,
-                          const SetLongDev *sl, uint64_t chunk) {
+// automaton where set_long_batch chose it (chunk its unit), else null.  rs:
+// the set, for a batched call (the on-demand DFA is its host object).
+static hipError_t run_set(rure_set *rs, const BatchDev &b, const DevTables &t, uint64_t *out, hipStream_t st,
+                          int dfa_grid, const SetLongDev *sl, uint64_t chunk) {
   if (sl) {
     uint64_t units = 0;
     const hipError_t e = launch_set_long(b, *sl, chunk, out, st, t.cus, &units);
@@ -502,6 +569,7 @@ static hipError_t run_set(const BatchDev &b, const DevTables &t, uint64_t *out, 
     return e;
   }
   note_set_units(0, 0, 0);
+  if (lazy_set_batch(rs, b, t)) return run_lazy_set(rs, b, t, out, st);
   if (!t.has_dfa) return run_pike(MODE_SET, false, b, t, out, st);
   const auto step = [&](const BatchDev &bq) {
     return t.use_cores ? launch_set_cores(bq, t.c, out, st, t.cus) : launch_dfa_set(bq, t.s, out, st, dfa_grid);
@@ -627,7 +695,7 @@ uint64_t set_single_call(rure_set *rs, const uint8_t *hay, size_t len, size_t st
   hipStream_t st = rs->stage.stream;
   if (len && !hip_ok(hipMemcpyAsync(rs->stage.hay, hay, len, hipMemcpyHostToDevice, st), &err)) die(err);
   BatchDev b{rs->stage.hay, nullptr, 0, len, 1, start};
-  if (!hip_ok(run_set(b, *t, rs->stage.res, st, 1, sl, chunk), &err)) die(err);
+  if (!hip_ok(run_set(nullptr, b, *t, rs->stage.res, st, 1, sl, chunk), &err)) die(err);
   uint64_t out = 0;
   if (!hip_ok(hipMemcpyAsync(&out, rs->stage.res, 8, hipMemcpyDeviceToHost, st), &err)) die(err);
   if (!hip_ok(hipStreamSynchronize(st), &err)) die(err);
@@ -696,7 +764,7 @@ int set_batch_word(rure_set *rs, const BatchDev &b, uint64_t *mask, hipStream_t 
   const SetLongDev *sl = set_long_batch(rs, b, t, &chunk);
   if (!sl && t->use_cores && !t->cores_adapted && !adapt_cores(rs, t, b, stream, &err)) return RURE_AMD_ERR_HIP;
   int grid = grid_for(b.count, t->s.lds_bytes, t->cus);
-  if (run_set(b, *t, mask, stream, grid, sl, chunk) != hipSuccess) return RURE_AMD_ERR_HIP;
+  if (run_set(rs, b, *t, mask, stream, grid, sl, chunk) != hipSuccess) return RURE_AMD_ERR_HIP;
   return RURE_AMD_OK;
 }
 

@@ -75,6 +75,15 @@ class Builder {
     return step_eof(keys_[s], &m);
   }
   bool lazy_match(uint32_t s) const { return s >= 2 && (keys_[s][0] & SF_MATCH); }
+  // Sets: the Match slots reported by the step into s, and those the EOF
+  // step from s reaches (DenseDfa::now_mask / eof_mask of the raw state).
+  bool lazy_is_set() const { return is_set_; }
+  uint64_t lazy_now(uint32_t s) const { return s >= 2 ? now_of(keys_[s]) : 0; }
+  uint64_t lazy_eof_mask(uint32_t s) {
+    uint64_t m = 0;
+    if (s >= 2) step_eof(keys_[s], &m);
+    return m;
+  }
   uint32_t lazy_start(int fi) const { return start_used_[fi] ? start_raw_[fi] : 0; }
 
   bool build(DenseDfa *out, std::string *err) {
@@ -701,6 +710,7 @@ LazyDfa::LazyDfa(const Program &prog, size_t max_bytes) : max_bytes_(max_bytes) 
   lim.max_raw_states = 0x7FFFFFF0;
   impl_ = new Impl(prog, lim);
   impl_->b.lazy_init(colmap, &ncol);
+  is_set = impl_->b.lazy_is_set();
   for (int i = 0; i < 128; ++i) start[i] = impl_->b.lazy_start(i);
   sync_new();
   for (int i = 0; i < 128; ++i) start[i] = entry_of(start[i]);
@@ -708,15 +718,23 @@ LazyDfa::LazyDfa(const Program &prog, size_t max_bytes) : max_bytes_(max_bytes) 
 
 LazyDfa::~LazyDfa() { delete impl_; }
 
+// sets: the states whose entry reports matches (the rule Builder numbers
+// [n_normal, n_match_end) by); a regex: the one-byte-delayed match flag
 uint32_t LazyDfa::entry_of(uint32_t s) const {
-  return s | (impl_->b.lazy_match(s) ? kLazyMatch : 0u);
+  const bool m = is_set ? now[s] != 0 : impl_->b.lazy_match(s);
+  return s | (m ? kLazyMatch : 0u);
 }
 
-// rows (unknown) and EOF flags for the states interned since the last call
+// rows (unknown), EOF flags and (sets) masks for the states interned since
+// the last call
 void LazyDfa::sync_new() {
   const uint32_t n = impl_->b.lazy_states();
   for (uint32_t s = (uint32_t)eof.size(); s < n; ++s) {
-    eof.push_back(impl_->b.lazy_eof(s) ? 1 : 0);
+    eof.push_back(!is_set && impl_->b.lazy_eof(s) ? 1 : 0);
+    if (is_set) {
+      now.push_back(impl_->b.lazy_now(s));
+      eof_mask.push_back(impl_->b.lazy_eof_mask(s));
+    }
     built.push_back(s < 2 ? 1 : 0);
     trans.resize((size_t)(s + 1) * ncol, s < 2 ? s : kLazyUnknown);
     if (s >= 2) todo_.push_back(s);
@@ -725,7 +743,7 @@ void LazyDfa::sync_new() {
 
 bool LazyDfa::build_row(uint32_t s) {
   if (s >= built.size() || built[s]) return true;
-  if (max_bytes_ && impl_->b.lazy_bytes() + trans.size() * 4 > max_bytes_) return false;
+  if (max_bytes_ && impl_->b.lazy_bytes() + trans.size() * 4 + now.size() * 16 > max_bytes_) return false;
   std::vector<uint32_t> row(ncol);
   impl_->b.lazy_row(s, row.data());
   sync_new();

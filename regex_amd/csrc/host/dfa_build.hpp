@@ -85,7 +85,10 @@ bool build_dense_dfa(const Program &prog, const DfaBuildLimits &lim, DenseDfa *o
 // state's id, | kLazyMatch when that state carries the (one-byte delayed)
 // match flag; kLazyUnknown for a row not built yet (the kernel parks the
 // lane there).  Columns are the program's byte classes (no quit states:
-// Unicode word boundaries keep the Pike VM).
+// Unicode word boundaries keep the Pike VM).  For a set program the match
+// bit marks the states whose entry reports matches (now != 0, the states
+// Builder numbers [n_normal, n_match_end)), now / eof_mask are
+// DenseDfa::now_mask / eof_mask of the raw states, and eof is unused.
 constexpr uint32_t kLazyMatch = 0x80000000u, kLazyUnknown = 0x7FFFFFFFu;
 class LazyDfa {
  public:
@@ -105,6 +108,9 @@ class LazyDfa {
   std::vector<uint32_t> trans;    // nstates * ncol entries
   std::vector<uint8_t> eof;       // per state: the EOF step yields a match
   std::vector<uint8_t> built;     // per state: its row is built
+  bool is_set = false;            // a set program: now / eof_mask per state (else empty)
+  std::vector<uint64_t> now;      // Match slots reported by the step into the state
+  std::vector<uint64_t> eof_mask; // Match slots the EOF step from the state reaches
  private:
   struct Impl;
   Impl *impl_ = nullptr;

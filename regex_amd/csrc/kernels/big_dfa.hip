@@ -7,7 +7,9 @@
 // -> leftmost start), start_flags (1415-1464); dispatch find_dfa_forward
 // (exec.rs:632-662) and shortest_dfa (exec.rs:692-694).  The reference
 // builds such automata lazily in a bounded cache; the host materialises them
-// eagerly (dfa_build.cpp, column form) so a lane only reads tables.
+// eagerly (dfa_build.cpp, column form) so a lane only reads tables.  Past
+// that budget too, rows are built on demand between rounds of
+// lazy_dfa_kernel (a regex) or lazy_set_kernel (a RegexSet's matches).
 //
 // Execution: one lane per haystack.  A 16-byte chunk's columns come from the
 // LDS column map first (independent of the state), then the dependent chain
@@ -257,7 +259,109 @@ hipError_t launch_lazy_m(const BatchDev &b, const LazyDfaDev &f, const RevDfaDev
   return hipGetLastError();
 }
 
+// RegexSet matches on a set's on-demand DFA (many_matches_at, exec.rs:
+// 998-1038 over dfa.rs:525-570): the walk of lazy_dfa_kernel, ORing up the
+// patterns each step reports as dfa_set_kernel does (now[] of the state
+// entered, a global u64 read taken only on entries with the match bit and
+// not on the chain from one state to the next), until the text ends (the
+// EOF step, dfa.rs:1004-1015: eof_mask[] of the last state), the automaton
+// dies or every pattern of the set is in the mask.  A parked lane carries
+// its mask in LazyPark::last.
+template <bool STRIDED>
+__global__ __launch_bounds__(1024) void lazy_set_kernel(BatchDev bt, LazyDfaDev f, uint64_t all, const LazyPark *in,
+                                                        uint64_t nin, LazyPark *park, unsigned long long *npark,
+                                                        uint64_t *out) {
+  __shared__ __attribute__((aligned(16))) uint32_t hot_rows[kBigLdsBytes / 4];
+  __shared__ uint8_t colmap[256];
+  const uint32_t nhot = f.hot * f.ncol;
+  for (uint32_t i = threadIdx.x; i < nhot; i += blockDim.x) hot_rows[i] = f.trans[i];
+  for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x) colmap[i] = f.colmap[i];
+  __syncthreads();
+  const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x, nl = in ? nin : bt.count;
+  for (uint64_t l = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; l < nl; l += nthreads) {
+    uint64_t h = l;
+    if (in) h = in[l].h;
+    const uint8_t *base;
+    uint64_t len;
+    if (STRIDED) {
+      base = bt.hay + h * bt.stride;
+      len = bt.length;
+    } else {
+      const uint64_t o0 = bt.offs[h], o1 = bt.offs[h + 1];
+      base = bt.hay + o0;
+      len = o1 - o0;
+    }
+    uint64_t mask = 0, p = bt.start;
+    bool done = bt.start > len, parked = false;  // done: no EOF step (dead, or nothing left to find)
+    uint32_t s = 0;
+    if (in) {
+      p = in[l].p;
+      mask = in[l].last;
+      s = in[l].s;
+    } else if (!done) {
+      const uint32_t e = f.start[fwd_flag_index(base, len, bt.start)];
+      s = e & ~kLazyMatchBit;
+      done = s == 0;  // dead start state (dfa.rs:484)
+    }
+    while (!done && p < len) {
+      const uintptr_t a = (uintptr_t)(base + p);
+      const uint4 v = *(const uint4 *)(a & ~(uintptr_t)15);
+      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+      const uint32_t j0 = (uint32_t)(a & 15);
+      const uint32_t n = (uint32_t)min<uint64_t>(16 - j0, len - p);
+      uint32_t j = j0;
+      for (; j < j0 + n; ++j) {
+        const uint32_t c = colmap[(w[j >> 2] >> (8 * (j & 3))) & 0xFF];
+        const uint32_t e = s < f.hot ? hot_rows[s * f.ncol + c] : f.trans[(size_t)s * f.ncol + c];
+        if (e == kLazyUnknownEntry) {
+          parked = true;
+          break;
+        }
+        if (e == 0) {
+          done = true;  // dead
+          break;
+        }
+        s = e & ~kLazyMatchBit;
+        if (e & kLazyMatchBit) {
+          mask |= f.now[s];
+          if ((mask & all) == all) {
+            done = true;
+            break;
+          }
+        }
+      }
+      p += j - j0;
+      if (parked) break;
+    }
+    if (parked) {
+      const unsigned long long k = atomicAdd(npark, 1ull);
+      LazyPark x;
+      x.h = h;
+      x.p = p;
+      x.last = mask;
+      x.s = s;
+      x.pad = 0;
+      park[k] = x;
+      continue;
+    }
+    out[h] = done ? mask : mask | f.eof_mask[s];
+  }
+}
+
 }  // namespace
+
+hipError_t launch_lazy_set(const BatchDev &b, const LazyDfaDev &f, uint64_t all, const LazyPark *in, uint64_t nin,
+                           LazyPark *park, unsigned long long *npark, uint64_t *out, hipStream_t st, int cus) {
+  if (b.count == 0 || (in && nin == 0)) return hipSuccess;
+  note_fwd_path(RURE_AMD_PATH_LAZY_DFA);
+  const uint64_t lanes = in ? nin : b.count;
+  const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>((lanes + 1023) / 1024, (uint64_t)cus * 2));
+  if (b.offs)
+    hipLaunchKernelGGL((lazy_set_kernel<false>), dim3(grid), dim3(1024), 0, st, b, f, all, in, nin, park, npark, out);
+  else
+    hipLaunchKernelGGL((lazy_set_kernel<true>), dim3(grid), dim3(1024), 0, st, b, f, all, in, nin, park, npark, out);
+  return hipGetLastError();
+}
 
 hipError_t launch_lazy_dfa(int mode, const BatchDev &b, const LazyDfaDev &f, const RevDfaDev &r, const LazyPark *in,
                            uint64_t nin, LazyPark *park, unsigned long long *npark, void *out, hipStream_t st,

@@ -614,15 +614,21 @@ uint32_t big_dfa_hot_rows(uint32_t ncol, uint32_t nstates);
 // A forward DFA built on demand (host LazyDfa): entries are next-state ids,
 // | 0x80000000 when that state carries the match flag, 0x7FFFFFFF for a row
 // not built yet; id 0 is the dead state.  The first `hot` rows sit in LDS.
+// A set's automaton: the bit marks a state whose entry reports matches, now /
+// eof_mask are the patterns reported on entering a state / at the end of the
+// text from it (null for a regex).
 struct LazyDfaDev {
   const uint32_t *trans;
   const uint8_t *colmap;      // 256 bytes
   const uint8_t *eof;         // per state
   const uint32_t *start;      // 128 start entries by flag index
   uint32_t ncol, hot;
+  const uint64_t *now;        // per state (sets)
+  const uint64_t *eof_mask;   // per state (sets)
 };
 // A lane stopped at a row not built yet: haystack, position of the byte it
-// needs, the last match end so far (~0: none), the state.
+// needs, the last match end so far (~0: none; a set: the mask collected so
+// far), the state.
 struct LazyPark {
   uint64_t h, p, last;
   uint32_t s, pad;
@@ -634,6 +640,12 @@ struct LazyPark {
 hipError_t launch_lazy_dfa(int mode, const BatchDev &b, const LazyDfaDev &f, const RevDfaDev &r, const LazyPark *in,
                            uint64_t nin, LazyPark *park, unsigned long long *npark, void *out, hipStream_t st,
                            int cus);
+// One round of RegexSet matches (many_matches_at, exec.rs:998-1038) on a
+// set's LazyDfaDev: out[h] = the mask of the patterns matching haystack h,
+// written by the round in which its lane finishes; `all` = every pattern of
+// the set (a lane stops once it has them all).  Lanes and parking as above.
+hipError_t launch_lazy_set(const BatchDev &b, const LazyDfaDev &f, uint64_t all, const LazyPark *in, uint64_t nin,
+                           LazyPark *park, unsigned long long *npark, uint64_t *out, hipStream_t st, int cus);
 uint32_t lazy_dfa_hot_rows(uint32_t ncol);
 
 // Scratch device memory for the scans, cached by the library (scratch.cpp):

@@ -86,11 +86,13 @@ struct DevTables {
   void *big_blob = nullptr; // their device copy
   struct rure *owner = nullptr;  // the regex (big_device builds its automata on first need)
   BigDfaDev bf{}, br{};
-  // the on-demand forward DFA (lazy_device / run_lazy): its device copy
-  // (grown as rows are built) and the reverse DFA it finds starts with
+  // the on-demand forward DFA (lazy_device / run_lazy; a set's: set_lazy /
+  // run_lazy_set, lazy_buf and lazy_cap only): its device copy (grown as
+  // rows are built) and the reverse DFA it finds starts with
   bool lazy_tried = false, has_lazy = false;
   void *lazy_buf = nullptr, *lazy_rblob = nullptr;
   size_t lazy_cap = 0;
+  size_t lazy_up_states = 0, lazy_up_built = 0;  // the table lazy_buf holds: its states and built rows (0: none)
   RevDfaDev lr{};
   // sets: the strip-built automaton of the chunked long scan (set_long_device),
   // uploaded on the first long call
@@ -293,6 +295,11 @@ struct rure_set {
   DenseDfa ldfa;
   PackedFwd lpf;
   std::vector<uint64_t> lreach;  // per state: the patterns any walk from it can still report
+  // the on-demand DFA (set_lazy; batches of a set without an eager DFA) and
+  // what its last batched call did: rounds run, 1 if the Pike VM answered
+  bool lazy_tried = false;
+  std::unique_ptr<LazyDfa> lazy;
+  uint32_t lazy_rounds = 0, lazy_fell_back = 0;
   NfaTables nt;
   bool nfa_ok = false;
   std::map<int, DevTables> dev;
@@ -353,6 +360,7 @@ bool big_device(const DevTables &tc);
 bool lazy_device(const DevTables &tc);
 DevTables *set_device(rure_set *rs, std::string *err);
 bool build_set_long(rure_set *rs);
+LazyDfa *set_lazy(rure_set *rs);
 const SetLongDev *set_long_device(rure_set *rs, DevTables *t, std::string *err);
 uint32_t first_byte_rule(const DenseDfa &d, uint32_t ustart1, bool nonempty, uint8_t bytes[4], bool *holds);
 bool run_class(const DenseDfa &d, uint32_t ustart1, bool nonempty, uint8_t cls[256], bool ascii);
