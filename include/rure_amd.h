@@ -201,7 +201,11 @@ int rure_amd_set_matches_batch_words(rure_set *re, const rure_amd_batch *batch, 
  * batches (documents of their own lengths) when a haystack has 256 KiB or
  * more to search, each haystack then cut by its own length.  An offset batch
  * synchronises the stream once to read the longest and the total length back
- * (16 bytes), and once more when it is chunked (the number of chunks). */
+ * (16 bytes), and once more when it is chunked (the number of chunks).  A
+ * regex whose forward DFA does not materialise runs, on batches of at least
+ * 64 haystacks per compute unit, one lane per haystack on its on-demand DFA
+ * (RURE_AMD_PATH_LAZY_DFA): synchronous, the host building the rows the text
+ * needs between rounds; past its memory budget the Pike VM answers. */
 int rure_amd_find_iter_batch(rure *re, const rure_amd_batch *batch, uint64_t *counts, rure_match *matches,
                              size_t capacity, uint64_t *total, void *stream);
 
@@ -425,7 +429,8 @@ int64_t rure_amd_set_program_export(rure_set *re, int which, rure_amd_prog_info 
 /* Export of a materialized DFA: trans = states*256 u32, eof_match = states
  * bytes, start = 128 u32.  which: 0 forward, 1 reverse, 2 the forward DFA
  * of the chunked find_iter (with stripped states, see _strip_export), 5 its
- * ASCII shadow. */
+ * ASCII shadow.  1 (and its rure_amd_dfa_info_get) also answers for a regex
+ * whose forward DFA did not materialise while the reverse one did. */
 int rure_amd_dfa_export(rure *re, int which, uint32_t *trans, uint8_t *eof_match,
                         uint32_t *start);
 /* Export of a set's DFA (rure_amd_set_dfa_info_get gives the sizes): trans =
@@ -467,6 +472,20 @@ int rure_amd_set_lazy_export(rure_set *re, rure_amd_lazy_info *info, uint32_t *t
  * in discovery order: what one round of a batched call does between two
  * launches.  Returns 1, 0 when the memory budget is spent, or an error. */
 int rure_amd_set_lazy_build(rure_set *re, const uint32_t *states, size_t n, size_t ahead);
+/* The same for a regex (host only, for tests): the on-demand forward DFA that
+ * answers find, is_match, shortest_match and find_iter over batches of a
+ * regex whose forward DFA does not materialise.  info as above, rounds and
+ * fell_back being those of the last batched find_iter that took it
+ * (fell_back: the other engines answered).  trans, built, start and colmap as
+ * above; the match bit marks a state entered one byte after a match ended
+ * (the reference's delayed match flag), eof = states bytes (1: the end of the
+ * text from the state is a match).  Match starts come from the reverse DFA
+ * (rure_amd_dfa_export, which = 1).  RURE_AMD_ERR_DFA where the regex gets no
+ * such automaton: a Unicode word boundary, a regex anchored at the end only
+ * (searched in reverse), no Pike VM tables, or no reverse DFA. */
+int rure_amd_lazy_export(rure *re, rure_amd_lazy_info *info, uint32_t *trans, uint8_t *eof, uint8_t *built,
+                         uint32_t *start, uint8_t *colmap);
+int rure_amd_lazy_build(rure *re, const uint32_t *states, size_t n, size_t ahead);
 /* Core form of a large set's DFA (used by the set kernel when the set DFA has
  * more than 255 ordinary or match-reporting states): sizes in info; lds =
  * 256-byte class map + (hot + 1) x K u16 entries (next core << 6 | output
@@ -619,7 +638,7 @@ typedef enum rure_amd_path {
   RURE_AMD_PATH_BIG_DFA = -6,           /* the big (u32) DFA */
   RURE_AMD_PATH_LINES = -8,             /* the ragged line kernel */
   RURE_AMD_PATH_SUFFIX_LONG = -9,       /* the chunked DfaSuffix scan */
-  RURE_AMD_PATH_LAZY_DFA = -10,         /* the on-demand DFA (a regex's, or a set's) */
+  RURE_AMD_PATH_LAZY_DFA = -10,         /* the on-demand DFA (a regex's searches or find_iter, or a set's) */
   RURE_AMD_PATH_SUFFIX_ITER = -11,      /* the DfaSuffix find_iter */
   RURE_AMD_PATH_ITER_LOOKS = -12,       /* the chunked find_iter of a look-around regex answered */
   RURE_AMD_PATH_ITER_LOOKS_QUIT = -13,  /* it quit: one haystack per wavefront answers */

@@ -872,6 +872,39 @@ class Regex(object):
             info["strip"] = strip
         return info, trans.reshape(n, 256), eof, start
 
+    def lazy_tables(self):
+        """The regex's on-demand forward DFA as it stands: (info, trans
+        (states, columns), eof, built, start, colmap); entries are next state
+        | 0x80000000 when a match ended one byte before (the delayed match
+        flag), 0 = dead, 0x7FFFFFFF = the row is not built yet.  info:
+        states, columns, rows_built, hot_rows, and rounds / fell_back of the
+        last batched find_iter that took it.  Raises RuntimeError where the
+        regex gets no such automaton (a Unicode word boundary, anchored at
+        the end only, no reverse DFA)."""
+        import numpy as np
+        info = N.LazyInfo()
+        _check(N.rure_amd_lazy_export(self._re, ctypes.byref(info), None, None, None, None, None), "lazy_export")
+        n, k = info.states, info.columns
+        trans = np.zeros(n * k, dtype=np.uint32)
+        eof = np.zeros(n, dtype=np.uint8)
+        built = np.zeros(n, dtype=np.uint8)
+        start = np.zeros(128, dtype=np.uint32)
+        colmap = np.zeros(256, dtype=np.uint8)
+        _check(N.rure_amd_lazy_export(self._re, ctypes.byref(info), trans.ctypes.data, eof.ctypes.data,
+                                      built.ctypes.data, start.ctypes.data, colmap.ctypes.data), "lazy_export")
+        d = {f: getattr(info, f) for f, _ in N.LazyInfo._fields_}
+        return d, trans.reshape(n, k), eof, built, start, colmap
+
+    def lazy_build(self, states, ahead=0):
+        """Builds the rows of `states` of the on-demand DFA, then `ahead` more
+        in discovery order (one round's host work); False once the memory
+        budget is spent."""
+        arr = (ctypes.c_uint32 * max(len(states), 1))(*[int(s) for s in states])
+        rc = N.rure_amd_lazy_build(self._re, arr, len(states), ahead)
+        if rc < 0:
+            _check(rc, "lazy_build")
+        return rc == 1
+
 
 def replace_all_chain(regexes, reps, haystack, length=None, capacity=None, stream=None):
     """replace_all of each regex in turn over one haystack, every step on the

@@ -238,6 +238,8 @@ class LazyInfo(ctypes.Structure):
 rure_amd_set_lazy_export = _sig("rure_amd_set_lazy_export", ctypes.c_int, VP, ctypes.POINTER(LazyInfo), VP, VP, VP,
                                 VP, VP, VP)
 rure_amd_set_lazy_build = _sig("rure_amd_set_lazy_build", ctypes.c_int, VP, VP, c_size, c_size)
+rure_amd_lazy_export = _sig("rure_amd_lazy_export", ctypes.c_int, VP, ctypes.POINTER(LazyInfo), VP, VP, VP, VP, VP)
+rure_amd_lazy_build = _sig("rure_amd_lazy_build", ctypes.c_int, VP, VP, c_size, c_size)
 rure_amd_debug_set = _sig("rure_amd_debug_set", ctypes.c_int, ctypes.c_char_p)
 rure_amd_first_byte_export = _sig("rure_amd_first_byte_export", ctypes.c_int, VP, VP)
 rure_amd_lex_export = _sig("rure_amd_lex_export", ctypes.c_int64, VP, VP, c_size, VP)

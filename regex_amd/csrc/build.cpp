@@ -836,11 +836,35 @@ bool big_device(const DevTables &tc) {
   return true;
 }
 
-// The on-demand forward DFA (host LazyDfa, big_dfa.hip lazy_dfa_kernel) for
-// automata past the eager budgets: built on the first batch that needs it.
-// Its reverse partner is the regular u16 reverse DFA (t.r, or drev packed
-// and uploaded here when the forward DFA did not materialise).  Programs
-// with a Unicode word boundary keep the Pike VM, as for the big automata.
+// The on-demand forward DFA (host LazyDfa; big_dfa.hip lazy_dfa_kernel and
+// lazy_iter_kernel) for automata past the eager budgets, created on the first
+// batch that needs it: the host half, which touches no device.  Its reverse
+// partner is the regular u16 reverse DFA, so that one must have materialised
+// without a quit state.  Programs with a Unicode word boundary keep the Pike
+// VM, as for the big automata; DfaAnchoredReverse regexes their reverse scan.
+// Null where the regex gets no such automaton.  The caller holds re->mu, and
+// build_regex has run.
+static LazyDfa *regex_lazy_locked(rure *re) {
+  if (re->lazy_tried) return re->lazy.get();
+  re->lazy_tried = true;
+  if (!re->nfa_ok || re->fwd.has_unicode_word_boundary || re->rev.has_unicode_word_boundary) return nullptr;
+  if (!re->nfa.anchored_start && re->nfa.anchored_end) return nullptr;  // DfaAnchoredReverse
+  if (!re->dfa_ok && (!re->rev_ok || re->drev.quit >= 0)) return nullptr;
+  size_t budget = kBigDfaBytes;
+  if (knob(Knob::BigBytes) > 0) budget = (size_t)knob(Knob::BigBytes);
+  re->lazy.reset(new LazyDfa(re->fwd, budget));
+  return re->lazy.get();
+}
+
+LazyDfa *regex_lazy(rure *re) {
+  if (!re || !build_regex(re)) return nullptr;
+  std::lock_guard<std::mutex> g(re->mu);
+  return regex_lazy_locked(re);
+}
+
+// Its device side: the reverse DFA it finds match starts with (t.r, or drev
+// packed and uploaded here when the forward DFA did not materialise); the
+// table itself is uploaded by the rounds (dispatch.cpp lazy_rounds).
 bool lazy_device(const DevTables &tc) {
   DevTables &t = const_cast<DevTables &>(tc);
   rure *re = t.owner;
@@ -848,12 +872,10 @@ bool lazy_device(const DevTables &tc) {
   std::lock_guard<std::mutex> g(re->mu);
   if (t.lazy_tried) return t.has_lazy;
   t.lazy_tried = true;
-  if (!re->nfa_ok || re->fwd.has_unicode_word_boundary || re->rev.has_unicode_word_boundary) return false;
-  if (!re->nfa.anchored_start && re->nfa.anchored_end) return false;  // DfaAnchoredReverse
+  if (!regex_lazy_locked(re)) return false;
   if (t.has_dfa) {
     t.lr = t.r;
   } else {
-    if (!re->rev_ok || re->drev.quit >= 0) return false;
     std::string e;
     if (re->pr.full.empty() && !pack_forward(re->drev, &re->pr, &e, true)) return false;
     const DenseDfa &rv = re->drev;
@@ -877,11 +899,6 @@ bool lazy_device(const DevTables &tc) {
     r.dead = rv.dead;
     r.quit = 0xFFFFFFFFu;
     r.ustart1 = re->pr.ustart1;
-  }
-  if (!re->lazy) {
-    size_t budget = kBigDfaBytes;
-    if (knob(Knob::BigBytes) > 0) budget = (size_t)knob(Knob::BigBytes);
-    re->lazy.reset(new LazyDfa(re->fwd, budget));
   }
   t.has_lazy = true;
   return true;

@@ -912,6 +912,11 @@ int rure_amd_dfa_info_get(rure *re, int which, rure_amd_dfa_info *info) {
     info->byte_classes = (int32_t)(which == 3 ? re->bfwd.ncol : re->brev.ncol);
     return RURE_AMD_OK;
   }
+  if (which == 1 && build_regex(re) && !re->dfa_ok && re->rev_ok) {
+    // the reverse DFA alone materialised: the on-demand forward DFA's partner
+    fill_info(re->drev, re->rev, 0, info);
+    return RURE_AMD_OK;
+  }
   if (!build_regex_dfas(re)) { info->ok = 0; return RURE_AMD_ERR_DFA; }
   if (which == 5) {  // the find_iter automaton's ASCII shadow (build_iter_dfa)
     if (!build_iter_dfa(re) || !re->iter_a_ok) { info->ok = 0; return RURE_AMD_ERR_DFA; }
@@ -1005,6 +1010,37 @@ int rure_amd_set_lazy_build(rure_set *rs, const uint32_t *states, size_t n, size
   LazyDfa *L = set_lazy(rs);
   if (!L) return RURE_AMD_ERR_DFA;
   std::lock_guard<std::mutex> g(rs->mu);
+  for (size_t i = 0; i < n; ++i) {
+    if (states[i] >= L->nstates()) return RURE_AMD_ERR_ARG;
+    if (!L->build_row(states[i])) return 0;
+  }
+  return L->expand(ahead) ? 1 : 0;
+}
+
+int rure_amd_lazy_export(rure *re, rure_amd_lazy_info *info, uint32_t *trans, uint8_t *eof, uint8_t *built,
+                         uint32_t *start, uint8_t *colmap) {
+  if (!re) return RURE_AMD_ERR_ARG;
+  if (info) memset(info, 0, sizeof(*info));
+  LazyDfa *L = regex_lazy(re);
+  if (!L) return RURE_AMD_ERR_DFA;
+  std::lock_guard<std::mutex> g(re->mu);
+  if (info)
+    *info = rure_amd_lazy_info{L->nstates(), L->ncol, (uint32_t)L->nbuilt(),
+                               std::min<uint32_t>(L->nstates(), lazy_dfa_hot_rows(L->ncol)), re->lazy_iter_rounds,
+                               re->lazy_iter_fell_back};
+  if (trans) memcpy(trans, L->trans.data(), L->trans.size() * 4);
+  if (eof) memcpy(eof, L->eof.data(), L->eof.size());
+  if (built) memcpy(built, L->built.data(), L->built.size());
+  if (start) memcpy(start, L->start, sizeof(L->start));
+  if (colmap) memcpy(colmap, L->colmap, 256);
+  return RURE_AMD_OK;
+}
+
+int rure_amd_lazy_build(rure *re, const uint32_t *states, size_t n, size_t ahead) {
+  if (!re || (!states && n)) return RURE_AMD_ERR_ARG;
+  LazyDfa *L = regex_lazy(re);
+  if (!L) return RURE_AMD_ERR_DFA;
+  std::lock_guard<std::mutex> g(re->mu);
   for (size_t i = 0; i < n; ++i) {
     if (states[i] >= L->nstates()) return RURE_AMD_ERR_ARG;
     if (!L->build_row(states[i])) return 0;
@@ -1111,7 +1147,7 @@ int rure_amd_dfa_strip_export(rure *re, uint32_t *strip) {
 
 int rure_amd_dfa_export(rure *re, int which, uint32_t *trans, uint8_t *eof_match, uint32_t *start) {
   if (!re) return RURE_AMD_ERR_ARG;
-  if (!build_regex_dfas(re)) return RURE_AMD_ERR_DFA;
+  if (!build_regex_dfas(re) && !(which == 1 && re->rev_ok)) return RURE_AMD_ERR_DFA;
   if ((which == 2 || which == 5) && !build_iter_dfa(re)) return RURE_AMD_ERR_DFA;
   if (which == 5 && !re->iter_a_ok) return RURE_AMD_ERR_DFA;
   const DenseDfa &d = which == 0 ? re->dfwd : which == 1 ? re->drev : which == 5 ? re->dfwd_iter_a : re->dfwd_iter;

@@ -294,9 +294,9 @@ static bool big_batch(const BatchDev &b, const DevTables &t) {
   return b.count >= (uint64_t)t.cus * 64;
 }
 
-// The rounds of a batched scan on an on-demand DFA (a regex's: run_lazy; a
-// set's: run_lazy_set): `launch` runs one round of the kernel; between
-// rounds the host builds the rows the parked lanes need (and, ahead of them,
+// The rounds of a batched scan on an on-demand DFA (a regex's: run_lazy and
+// run_lazy_iter; a set's: run_lazy_set): `launch` runs one round of the
+// kernel; between rounds the host builds the rows the parked lanes need (and, ahead of them,
 // more rows in discovery order) and uploads the grown table, which stays in
 // t.lazy_buf for the next call.  Synchronous, as the reference's
 // construction happens inside its search.  The reference gives up on its
@@ -304,9 +304,11 @@ static bool big_batch(const BatchDev &b, const DevTables &t) {
 // here a spent memory budget or kLazyRounds rounds do the same for the batch:
 // *ok is then false and the caller runs the Pike VM over the whole batch
 // (the rounds' scratch is freed by then).  *rounds = the rounds launched.
+// Park is the kernel's record of a parked lane (LazyPark, LazyIterPark): the
+// rounds read its state `s` and hand the records back to the next launch.
 // The caller holds the lock of L's owner.
 constexpr int kLazyRounds = 256;
-template <class Launch>
+template <class Park, class Launch>
 static hipError_t lazy_rounds(LazyDfa &L, DevTables &t, uint64_t count, hipStream_t st, bool *ok_out, uint32_t *rounds,
                               Launch launch) {
   size_t ahead = 4096;  // rows built ahead per round (knob lazy_rows: tests)
@@ -315,15 +317,15 @@ static hipError_t lazy_rounds(LazyDfa &L, DevTables &t, uint64_t count, hipStrea
   *ok_out = ok;
   *rounds = 0;
   hipError_t e = hipSuccess;
-  Scratch<LazyPark> pk[2];
+  Scratch<Park> pk[2];
   Scratch<unsigned long long> cnt;
-  const size_t pbytes = std::max<uint64_t>(count, 1) * sizeof(LazyPark);
+  const size_t pbytes = std::max<uint64_t>(count, 1) * sizeof(Park);
   if ((e = pk[0].alloc(pbytes, st)) != hipSuccess) return e;
   if ((e = pk[1].alloc(pbytes, st)) != hipSuccess) return e;
   if ((e = cnt.alloc(16, st)) != hipSuccess) return e;
-  const LazyPark *in = nullptr;
+  const Park *in = nullptr;
   uint64_t nin = 0;
-  std::vector<LazyPark> host;
+  std::vector<Park> host;
   for (int round = 0; ok && e == hipSuccess; ++round) {
     // the table: [colmap 256][start 512][now cap * 8][eof_mask cap * 8][eof cap][trans cap * ncol * 4]
     // (now and eof_mask: a set's, 8-byte aligned; none for a regex)
@@ -364,7 +366,7 @@ static hipError_t lazy_rounds(LazyDfa &L, DevTables &t, uint64_t count, hipStrea
     f.trans = (const uint32_t *)(base + o_trans);
     f.ncol = L.ncol;
     f.hot = std::min<uint32_t>((uint32_t)ns, lazy_dfa_hot_rows(L.ncol));
-    LazyPark *po = pk[round & 1].get();
+    Park *po = pk[round & 1].get();
     if ((e = hipMemsetAsync(cnt.get(), 0, 8, st)) != hipSuccess) break;
     if ((e = launch(f, in, nin, po, cnt.get())) != hipSuccess) break;
     *rounds = (uint32_t)round + 1;
@@ -374,10 +376,10 @@ static hipError_t lazy_rounds(LazyDfa &L, DevTables &t, uint64_t count, hipStrea
     if (n == 0) break;
     if (round + 1 >= kLazyRounds) { ok = false; break; }
     host.resize(n);
-    if ((e = hipMemcpyAsync(host.data(), po, n * sizeof(LazyPark), hipMemcpyDeviceToHost, st)) != hipSuccess ||
+    if ((e = hipMemcpyAsync(host.data(), po, n * sizeof(Park), hipMemcpyDeviceToHost, st)) != hipSuccess ||
         (e = hipStreamSynchronize(st)) != hipSuccess)
       break;
-    for (const LazyPark &x : host)
+    for (const Park &x : host)
       if (!(ok = L.build_row(x.s))) break;
     // (a fixed number ahead: doubling the rows built ahead each round built
     // states in discovery order the text never visits, seconds of host work
@@ -399,7 +401,7 @@ static hipError_t run_lazy(int mode, const BatchDev &b, const DevTables &tc, voi
   std::lock_guard<std::mutex> g(re->mu);
   bool ok = true;
   uint32_t rounds = 0;
-  const hipError_t e = lazy_rounds(*re->lazy, t, b.count, st, &ok, &rounds,
+  const hipError_t e = lazy_rounds<LazyPark>(*re->lazy, t, b.count, st, &ok, &rounds,
                                    [&](const LazyDfaDev &f, const LazyPark *in, uint64_t nin, LazyPark *po,
                                        unsigned long long *cnt) {
                                      return launch_lazy_dfa(mode, b, f, t.lr, in, nin, po, cnt, out, st, t.cus);
@@ -415,6 +417,49 @@ static bool lazy_batch(const BatchDev &b, const DevTables &t) {
   const bool force = knob(Knob::Lazy) == 1;
   if (!force && (t.has_dfa || !big_batch(b, t))) return false;
   return lazy_device(t);
+}
+
+// The batched find_iter on the on-demand forward DFA (lazy_batch's regexes):
+// rounds of lazy_iter_kernel's count form until no lane is parked, the counts
+// scanned to offsets, its write form once, then the counts and total as the
+// wave path makes them.  *taken = false where the on-demand DFA gave the batch
+// up (a spent budget, kLazyRounds, or the write form met a row not built):
+// nothing of the outputs is the answer, no scratch is held, and the caller's
+// other engines run the batch.
+static hipError_t run_lazy_iter(rure *re, DevTables &t, const BatchDev &b, const IterOut &o, hipStream_t st,
+                                bool *taken) {
+  *taken = false;
+  std::lock_guard<std::mutex> g(re->mu);
+  const auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t sz_counts = al((b.count + 1) * 4), sz_off = al((b.count + 1) * 8);
+  Scratch<uint8_t> buf;
+  hipError_t e = buf.alloc(sz_counts + sz_off + 256, st);
+  if (e != hipSuccess) return e;
+  uint32_t *counts = (uint32_t *)buf.get(), *flag = (uint32_t *)(buf.get() + sz_counts + sz_off);
+  uint64_t *off = (uint64_t *)(buf.get() + sz_counts);
+  if ((e = hipMemsetAsync(counts + b.count, 0, 4, st)) != hipSuccess) return e;
+  if ((e = hipMemsetAsync(flag, 0, 4, st)) != hipSuccess) return e;
+  bool ok = true;
+  LazyDfaDev table{};  // the last round's: every row the batch reads is in it
+  e = lazy_rounds<LazyIterPark>(*re->lazy, t, b.count, st, &ok, &re->lazy_iter_rounds,
+                                [&](const LazyDfaDev &f, const LazyIterPark *in, uint64_t nin, LazyIterPark *po,
+                                    unsigned long long *cnt) {
+                                  table = f;
+                                  return launch_lazy_iter_count(b, f, t.lr, in, nin, po, cnt, counts, st, t.cus);
+                                });
+  re->lazy_iter_fell_back = e == hipSuccess && !ok;
+  if (e != hipSuccess || !ok) return e;
+  uint32_t unknown = 0;
+  if ((e = scan_counts(counts, off, b.count, st)) != hipSuccess) return e;
+  if ((e = launch_lazy_iter_write(b, table, t.lr, off, o.matches, o.cap, flag, st, t.cus)) != hipSuccess) return e;
+  if ((e = hipMemcpyAsync(&unknown, flag, 4, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+  if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
+  if (unknown) {
+    re->lazy_iter_fell_back = 1;
+    return hipSuccess;
+  }
+  *taken = true;
+  return launch_iter_counts(b, off, o, st, t.cus);
 }
 
 // Offset batches (documents of their own lengths) of find / is_match /
@@ -532,7 +577,7 @@ static hipError_t run_lazy_set(rure_set *rs, const BatchDev &b, const DevTables 
   const size_t np = rs->exprs.size();
   const uint64_t all = np >= 64 ? ~0ull : (1ull << np) - 1;
   bool ok = true;
-  const hipError_t e = lazy_rounds(*rs->lazy, t, b.count, st, &ok, &rs->lazy_rounds,
+  const hipError_t e = lazy_rounds<LazyPark>(*rs->lazy, t, b.count, st, &ok, &rs->lazy_rounds,
                                    [&](const LazyDfaDev &f, const LazyPark *in, uint64_t nin, LazyPark *po,
                                        unsigned long long *cnt) {
                                      return launch_lazy_set(b, f, all, in, nin, po, cnt, out, st, t.cus);
@@ -596,8 +641,9 @@ static hipError_t caps_grid(size_t units, const DevTables &t, uint32_t ns, hipSt
 // kept, not resolved), then the Pike VM with slots: from the match start over
 // the text up to two characters past the match end, or over the whole
 // haystack where the DFA quit and for anchored-start programs.  A regex whose
-// DFA does not materialise takes its bounds from the Pike VM (the reference's
-// lazy DFA would have produced them).
+// DFA does not materialise takes its bounds from the on-demand DFA on batches
+// that fill the device (lazy_batch; the reference's lazy DFA produces them),
+// else from the Pike VM.
 hipError_t run_captures(const BatchDev &b, const DevTables &t, uint64_t *slots, uint32_t ns, hipStream_t st,
                         int dfa_grid) {
   if (ns <= 2) return run_regex(MODE_FIND, b, t, slots, st, dfa_grid);
@@ -607,7 +653,8 @@ hipError_t run_captures(const BatchDev &b, const DevTables &t, uint64_t *slots, 
     if ((e = found.alloc(b.count * 16, st)) != hipSuccess) return e;
     e = lane_search_ok(t) ? launch_lane_search(MODE_FIND, b, t.m, t.f, t.r, found.get(), st, t.cus)
         : t.has_dfa       ? run_dfa_step(MODE_FIND, b, t, found.get(), st, dfa_grid, nullptr)
-                          : run_pike(MODE_FIND, false, b, t, found.get(), st);
+        : lazy_batch(b, t) ? run_lazy(MODE_FIND, b, t, found.get(), st)
+                           : run_pike(MODE_FIND, false, b, t, found.get(), st);
   }
   int grid = 1;
   Scratch<> scratch;
@@ -992,6 +1039,16 @@ hipError_t run_find_iter(rure *re, DevTables *t, const BatchDev &b, const IterOu
                           build_iter_dfa(re) && re->suffix_fwd;
   if (lane_search_ok(*t) && re->nfa_ok && !suffix_fwd)
     return launch_find_iter_wave(b, t->has_dfa ? &t->f : nullptr, t->r, t->n, o, st, t->cus, sp, &t->m);
+  // A regex whose forward DFA did not materialise, on a batch that fills the
+  // device (lazy_batch; knob lazy=1: any regex that can have it, ahead of the
+  // chunked engines): every search of the iteration on the on-demand DFA, as
+  // the reference's lazy DFA serves them whatever the state count.  Whole
+  // haystacks only.  Where it gives the batch up, the engines below answer.
+  if (!sp && b.count && !lane_search_ok(*t) && lazy_batch(b, *t)) {
+    bool taken = false;
+    const hipError_t e = run_lazy_iter(re, *t, b, o, st, &taken);
+    if (e != hipSuccess || taken) return e;
+  }
   // Chunked speculative iteration (iter_scan.hip); otherwise one wave per
   // haystack.  With look-around (or a DFA that can quit) it needs the
   // stripped states (not an anchored regex) and a whole haystack (no span:

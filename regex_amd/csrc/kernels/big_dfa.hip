@@ -9,7 +9,8 @@
 // builds such automata lazily in a bounded cache; the host materialises them
 // eagerly (dfa_build.cpp, column form) so a lane only reads tables.  Past
 // that budget too, rows are built on demand between rounds of
-// lazy_dfa_kernel (a regex) or lazy_set_kernel (a RegexSet's matches).
+// lazy_dfa_kernel (a regex), lazy_iter_kernel (its find_iter) or
+// lazy_set_kernel (a RegexSet's matches).
 //
 // Execution: one lane per haystack.  A 16-byte chunk's columns come from the
 // LDS column map first (independent of the state), then the dependent chain
@@ -259,6 +260,150 @@ hipError_t launch_lazy_m(const BatchDev &b, const LazyDfaDev &f, const RevDfaDev
   return hipGetLastError();
 }
 
+// find_iter on the on-demand DFA (re_trait.rs:197-221 over find_dfa_forward,
+// exec.rs:632-662): one lane per haystack runs the whole iteration, every
+// search the walk of lazy_dfa_kernel<MODE_FIND> from the iteration's position
+// ip.  A search without a match ends the iteration: ip past the end, a dead
+// start state, no match end, or a reverse NoMatch (exec.rs:656-660).  The
+// step rule is iter_scan.hip iter_next's: an empty match moves ip to e + 1
+// and is skipped when it ends where the last match did, any other match
+// moves ip to its end.  Every pass of the loop leaves it, consumes a byte or
+// ends a search, and a search that ends leaves the loop or raises ip.
+//
+// WRITE = false counts: a lane that meets a row not built yet parks with the
+// iteration's state (ip, lm, count) and the search's (p, s, last), and the
+// next round resumes it inside that search; a lane that finishes writes
+// counts[h].  WRITE = true runs once after the counts are scanned to off:
+// match k of haystack h goes to record off[h] + k when that is below cap.
+// The walk is the count form's, so every row it reads is built; should it
+// read an unknown entry all the same, it sets *flag and the lane stops.
+template <bool WRITE, bool STRIDED>
+__global__ __launch_bounds__(1024) void lazy_iter_kernel(BatchDev bt, LazyDfaDev f, RevDfaDev r,
+                                                         const LazyIterPark *in, uint64_t nin, LazyIterPark *park,
+                                                         unsigned long long *npark, uint32_t *counts,
+                                                         const uint64_t *off, uint64_t *matches, uint64_t cap,
+                                                         uint32_t *flag) {
+  __shared__ __attribute__((aligned(16))) uint32_t hot_rows[kBigLdsBytes / 4];
+  __shared__ uint8_t colmap[256];
+  const uint32_t nhot = f.hot * f.ncol;
+  for (uint32_t i = threadIdx.x; i < nhot; i += blockDim.x) hot_rows[i] = f.trans[i];
+  for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x) colmap[i] = f.colmap[i];
+  __syncthreads();
+  const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x, nl = in ? nin : bt.count;
+  for (uint64_t l = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; l < nl; l += nthreads) {
+    uint64_t h = l;
+    if (in) h = in[l].h;
+    const uint8_t *base;
+    uint64_t len;
+    if (STRIDED) {
+      base = bt.hay + h * bt.stride;
+      len = bt.length;
+    } else {
+      const uint64_t o0 = bt.offs[h], o1 = bt.offs[h + 1];
+      base = bt.hay + o0;
+      len = o1 - o0;
+    }
+    uint64_t ip = bt.start, lm = NONE, cnt = 0;  // the iteration
+    uint64_t p = 0, last = NONE;                 // the search
+    uint32_t s = 0;
+    bool searching = false, parked = false;
+    if (in) {
+      ip = in[l].ip;
+      lm = in[l].lm;
+      cnt = in[l].count;
+      p = in[l].p;
+      last = in[l].last;
+      s = in[l].s;
+      searching = true;
+    }
+    // One loop for the whole iteration, a 16-byte block of a search per pass:
+    // a lane whose search ends finds its start and begins the next search
+    // inside the pass and walks on beside the wave's other lanes (a walk loop
+    // inside a search loop made the whole wave wait for the slowest walk
+    // before any lane could begin its next search: 1.9 times the time on
+    // text where nearly every wave holds a match).
+    while (true) {
+      if (!searching) {
+        if (ip > len) break;
+        s = f.start[fwd_flag_index(base, len, ip)] & ~kLazyMatchBit;
+        if (s == 0) break;  // dead start state (dfa.rs:484)
+        p = ip;
+        last = NONE;
+        searching = true;
+      }
+      bool done = false;
+      if (p < len) {
+        const uintptr_t a = (uintptr_t)(base + p);
+        const uint4 v = *(const uint4 *)(a & ~(uintptr_t)15);
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+        const uint32_t j0 = (uint32_t)(a & 15);
+        const uint32_t n = (uint32_t)min<uint64_t>(16 - j0, len - p);
+        uint32_t j = j0;
+        for (; j < j0 + n; ++j) {
+          const uint32_t c = colmap[(w[j >> 2] >> (8 * (j & 3))) & 0xFF];
+          const uint32_t e = s < f.hot ? hot_rows[s * f.ncol + c] : f.trans[(size_t)s * f.ncol + c];
+          if (e == kLazyUnknownEntry) {
+            parked = true;
+            break;
+          }
+          if (e == 0) {
+            done = true;  // dead
+            break;
+          }
+          s = e & ~kLazyMatchBit;
+          if (e & kLazyMatchBit) last = p + (j - j0);  // dfa.rs:658-668: Match(at - 1)
+        }
+        p += j - j0;
+        if (parked) break;
+        if (!done && p < len) continue;  // the next block
+      }
+      // the search is over: the automaton died, or the text ended
+      searching = false;
+      if (!done && f.eof[s]) last = len;  // dfa.rs:748-763
+      if (last == NONE) break;
+      uint64_t ms = ip;  // exec.rs:647
+      if (last != ip) {
+        ms = rev_scan(r, nullptr, base, len, ip, last);
+        if (ms == NONE || ms == QUITMARK) break;  // exec.rs:656-660 (no quit state here)
+      }
+      if (ms == last) {
+        ip = last + 1;
+        if (lm == last) continue;
+      } else {
+        ip = last;
+      }
+      lm = last;
+      if (WRITE) {
+        const uint64_t k = off[h] + cnt;
+        if (k < cap) {
+          matches[2 * k] = ms;
+          matches[2 * k + 1] = last;
+        }
+      }
+      ++cnt;
+    }
+    if (parked) {
+      if (WRITE) {
+        *flag = 1;
+        continue;
+      }
+      const unsigned long long k = atomicAdd(npark, 1ull);
+      LazyIterPark x;
+      x.h = h;
+      x.ip = ip;
+      x.lm = lm;
+      x.p = p;
+      x.last = last;
+      x.count = cnt;
+      x.s = s;
+      x.pad = 0;
+      park[k] = x;
+      continue;
+    }
+    if (!WRITE) counts[h] = (uint32_t)cnt;
+  }
+}
+
 // RegexSet matches on a set's on-demand DFA (many_matches_at, exec.rs:
 // 998-1038 over dfa.rs:525-570): the walk of lazy_dfa_kernel, ORing up the
 // patterns each step reports as dfa_set_kernel does (now[] of the state
@@ -373,6 +518,37 @@ hipError_t launch_lazy_dfa(int mode, const BatchDev &b, const LazyDfaDev &f, con
     case MODE_ISMATCH: return launch_lazy_m<MODE_ISMATCH>(b, f, r, in, nin, park, npark, out, st, cus);
     default: return launch_lazy_m<MODE_SHORTEST>(b, f, r, in, nin, park, npark, out, st, cus);
   }
+}
+
+hipError_t launch_lazy_iter_count(const BatchDev &b, const LazyDfaDev &f, const RevDfaDev &r, const LazyIterPark *in,
+                                  uint64_t nin, LazyIterPark *park, unsigned long long *npark, uint32_t *counts,
+                                  hipStream_t st, int cus) {
+  if (b.count == 0 || (in && nin == 0)) return hipSuccess;
+  note_fwd_path(RURE_AMD_PATH_LAZY_DFA);
+  const uint64_t lanes = in ? nin : b.count;
+  const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>((lanes + 1023) / 1024, (uint64_t)cus * 2));
+  if (b.offs)
+    hipLaunchKernelGGL((lazy_iter_kernel<false, false>), dim3(grid), dim3(1024), 0, st, b, f, r, in, nin, park, npark,
+                       counts, (const uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t)0, (uint32_t *)nullptr);
+  else
+    hipLaunchKernelGGL((lazy_iter_kernel<false, true>), dim3(grid), dim3(1024), 0, st, b, f, r, in, nin, park, npark,
+                       counts, (const uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t)0, (uint32_t *)nullptr);
+  return hipGetLastError();
+}
+
+hipError_t launch_lazy_iter_write(const BatchDev &b, const LazyDfaDev &f, const RevDfaDev &r, const uint64_t *off,
+                                  uint64_t *matches, uint64_t cap, uint32_t *flag, hipStream_t st, int cus) {
+  if (b.count == 0) return hipSuccess;
+  const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>((b.count + 1023) / 1024, (uint64_t)cus * 2));
+  if (b.offs)
+    hipLaunchKernelGGL((lazy_iter_kernel<true, false>), dim3(grid), dim3(1024), 0, st, b, f, r,
+                       (const LazyIterPark *)nullptr, (uint64_t)0, (LazyIterPark *)nullptr,
+                       (unsigned long long *)nullptr, (uint32_t *)nullptr, off, matches, cap, flag);
+  else
+    hipLaunchKernelGGL((lazy_iter_kernel<true, true>), dim3(grid), dim3(1024), 0, st, b, f, r,
+                       (const LazyIterPark *)nullptr, (uint64_t)0, (LazyIterPark *)nullptr,
+                       (unsigned long long *)nullptr, (uint32_t *)nullptr, off, matches, cap, flag);
+  return hipGetLastError();
 }
 
 uint32_t lazy_dfa_hot_rows(uint32_t ncol) { return kBigLdsBytes / 4 / std::max<uint32_t>(ncol, 1); }

@@ -647,6 +647,32 @@ hipError_t launch_lazy_dfa(int mode, const BatchDev &b, const LazyDfaDev &f, con
 hipError_t launch_lazy_set(const BatchDev &b, const LazyDfaDev &f, uint64_t all, const LazyPark *in, uint64_t nin,
                            LazyPark *park, unsigned long long *npark, uint64_t *out, hipStream_t st, int cus);
 uint32_t lazy_dfa_hot_rows(uint32_t ncol);
+// A find_iter lane stopped at a row not built yet: the haystack, the
+// iteration's state (ip: the start of the search under way, lm: the end of
+// the last match or ~0, count: the matches so far) and that search's (p: the
+// position of the byte it needs, last: its last match end so far or ~0, s:
+// the state).
+struct LazyIterPark {
+  uint64_t h, ip, lm, p, last, count;
+  uint32_t s, pad;
+};
+// The batched find_iter (re_trait.rs:197-221) on a regex's LazyDfaDev, one
+// lane per haystack.  The count form runs in rounds as launch_lazy_dfa:
+// counts[h] (u32) is written by the round in which haystack h's lane
+// finishes.  The write form runs once when no lane is parked any more, over
+// off = the exclusive sums of counts: match k of haystack h goes to record
+// off[h] + k when that is below cap.  *flag (device, zeroed) is set should
+// the write form meet a row not built: its records are then not the answer.
+hipError_t launch_lazy_iter_count(const BatchDev &b, const LazyDfaDev &f, const RevDfaDev &r, const LazyIterPark *in,
+                                  uint64_t nin, LazyIterPark *park, unsigned long long *npark, uint32_t *counts,
+                                  hipStream_t st, int cus);
+hipError_t launch_lazy_iter_write(const BatchDev &b, const LazyDfaDev &f, const RevDfaDev &r, const uint64_t *off,
+                                  uint64_t *matches, uint64_t cap, uint32_t *flag, hipStream_t st, int cus);
+// The tail of the one-lane-per-haystack find_iter engines (iter_scan.hip):
+// off[0..n] = the exclusive sums of counts[0..n) (u32; off[n] = their
+// total), and from them o.counts per haystack and o.total.
+hipError_t scan_counts(const uint32_t *counts, uint64_t *off, uint64_t n, hipStream_t st);
+hipError_t launch_iter_counts(const BatchDev &b, const uint64_t *off, const IterOut &o, hipStream_t st, int cus);
 
 // Scratch device memory for the scans, cached by the library (scratch.cpp):
 // a freed block is kept with an event recorded on the freeing stream and

@@ -2607,6 +2607,8 @@ __global__ __launch_bounds__(256) void iter_ragged_units_kernel(BatchDev b, uint
   nk[h] = v;
 }
 
+}  // namespace
+
 hipError_t scan_counts(const uint32_t *counts, uint64_t *off, uint64_t n, hipStream_t st) {
   // off[0..n] = exclusive prefix sums of counts[0..n) (off[n] = total)
   size_t tmp = 0;
@@ -2620,7 +2622,11 @@ hipError_t scan_counts(const uint32_t *counts, uint64_t *off, uint64_t n, hipStr
   return e != hipSuccess ? e : e2;
 }
 
-}  // namespace
+hipError_t launch_iter_counts(const BatchDev &b, const uint64_t *off, const IterOut &o, hipStream_t st, int cus) {
+  hipLaunchKernelGGL(iter_counts_kernel, dim3(grid_cap(b.count, 256, cus, 4)), dim3(256), 0, st, b.count,
+                     (uint64_t)1, (const uint64_t *)nullptr, off, o.counts, o.total, b);
+  return hipGetLastError();
+}
 
 // Lexer engine (terminal matches + first-byte rule); RURE_AMD_LEX=0 disables.
 // (haystacks below 4 GiB: the lexer's records are u32 offsets from the unit
@@ -3277,9 +3283,7 @@ hipError_t launch_find_iter_wave(const BatchDev &b, const FwdDfaDev *f, const Re
                        (const uint64_t *)off, o.matches, o.cap, scr,
                        spn ? spn->entry : (const uint64_t *)nullptr, hi, (uint64_t *)nullptr, md);
     if ((e = hipGetLastError()) != hipSuccess) break;
-    hipLaunchKernelGGL(iter_counts_kernel, dim3(grid_cap(b.count, 256, cus, 4)), dim3(256), 0, st, b.count,
-                       (uint64_t)1, (const uint64_t *)nullptr, off, o.counts, o.total, b);
-    e = hipGetLastError();
+    e = launch_iter_counts(b, off, o, st, cus);
   } while (false);
   hipError_t e2 = scratch_free(buf, st);
   return e != hipSuccess ? e : e2;

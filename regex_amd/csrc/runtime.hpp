@@ -234,8 +234,12 @@ struct rure {
   bool big_ok = false, big_built = false;
   DenseDfa bfwd, brev;
   bool rev_ok = false;            // drev materialised (even when dfwd did not)
-  bool lazy_tried = false;        // the on-demand forward DFA (lazy_device)
+  // the on-demand forward DFA (regex_lazy; its device side: lazy_device) and
+  // what the last batched find_iter on it did: rounds run, 1 if it gave the
+  // batch up and the other engines answered
+  bool lazy_tried = false;
   std::unique_ptr<LazyDfa> lazy;
+  uint32_t lazy_iter_rounds = 0, lazy_iter_fell_back = 0;
   NfaTables nt;
   bool nfa_ok = false;
   std::map<int, DevTables> dev;
@@ -358,6 +362,7 @@ void set_prefix_skip(const rure *re, FwdDfaDev *f);
 DevTables *regex_device(rure *re, std::string *err);
 bool big_device(const DevTables &tc);
 bool lazy_device(const DevTables &tc);
+LazyDfa *regex_lazy(rure *re);
 DevTables *set_device(rure_set *rs, std::string *err);
 bool build_set_long(rure_set *rs);
 LazyDfa *set_lazy(rure_set *rs);
