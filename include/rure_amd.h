@@ -158,7 +158,20 @@ typedef struct rure_amd_batch {
  * answers the search and cannot quit; RegexSets, regexes with a Unicode word
  * boundary, of the DfaSuffix or anchored-start Literal match types, or
  * anchored at the start keep one lane per haystack of an offset batch
- * (end-anchored ones read only the match from the end). */
+ * (end-anchored ones read only the match from the end).
+ * A regex whose forward DFA does not materialise (past the eager state
+ * budgets) runs on its on-demand DFA (RURE_AMD_PATH_LAZY_DFA), and these
+ * calls are then synchronous: the host builds the rows the text needs between
+ * rounds of the kernel and waits for each round.  Batches of at least 64
+ * haystacks per compute unit run one lane per haystack; fixed-stride batches
+ * of fewer than 128 haystacks per compute unit with 256 KiB or more to search
+ * in each (a log buffer, one document; rure_is_match, rure_find and
+ * rure_shortest_match on such a host buffer too) are cut into units as
+ * above, which step into a state's twin without the unanchored prefix at
+ * their cut (rure_amd_last_lazy_long tells).  Past the automaton's memory
+ * budget, or after 256 rounds, the Pike VM answers the whole batch.  Other
+ * batches of such a regex (offset batches, a regex anchored at the start)
+ * run on the Pike VM, a wave per haystack. */
 /* Batched rure_find: out[i] = leftmost-first match, or {SIZE_MAX, SIZE_MAX}. */
 int rure_amd_find_batch(rure *re, const rure_amd_batch *batch, rure_match *out, void *stream);
 /* Batched rure_is_match: out[i] in {0, 1}. */
@@ -486,6 +499,19 @@ int rure_amd_set_lazy_build(rure_set *re, const uint32_t *states, size_t n, size
 int rure_amd_lazy_export(rure *re, rure_amd_lazy_info *info, uint32_t *trans, uint8_t *eof, uint8_t *built,
                          uint32_t *start, uint8_t *colmap);
 int rure_amd_lazy_build(rure *re, const uint32_t *states, size_t n, size_t ahead);
+/* The strip links of that automaton (host only, for tests): strip = one u32
+ * per state (`states` entries of rure_amd_lazy_export's info), the id of the
+ * state's twin without the threads of the unanchored prefix (no match bit),
+ * 0 = dead, 0x7FFFFFFF = not computed yet.  A chunked scan of long haystacks
+ * steps into the twin at a unit's cut, so that only matches started inside
+ * the unit go on.  Links are made on demand: a new twin is numbered after
+ * every existing state with its row not built, and is its own twin; states,
+ * rows and flags that existed stay as they were.  RURE_AMD_ERR_DFA where the
+ * regex has no on-demand automaton or is anchored at the start (no prefix). */
+int rure_amd_lazy_strip_export(rure *re, uint32_t *strip);
+/* Makes the links of the n named states.  Returns 1, 0 when the memory
+ * budget is spent, or an error. */
+int rure_amd_lazy_strip_build(rure *re, const uint32_t *states, size_t n);
 /* Core form of a large set's DFA (used by the set kernel when the set DFA has
  * more than 255 ordinary or match-reporting states): sizes in info; lds =
  * 256-byte class map + (hot + 1) x K u16 entries (next core << 6 | output
@@ -682,6 +708,15 @@ uint64_t rure_amd_last_long_units(uint64_t *haystacks, uint64_t *chunk);
  * 64-pattern group's, for larger sets) that did not chunk.  The host knows
  * the geometry: this call waits for nothing. */
 uint64_t rure_amd_last_set_units(uint64_t *haystacks, uint64_t *chunk);
+/* Diagnostics (host only, one value for the whole process likewise): the
+ * units the last chunked find / is_match / shortest_match (or captures
+ * bounds) call on a regex's on-demand DFA cut its batch into; *haystacks =
+ * that batch's haystack count, *chunk = the unit size in bytes, *rounds = the
+ * kernel rounds it ran, *fell_back = 1 when the Pike VM answered instead
+ * (any may be NULL).  All 0 before the first such call and after a regex
+ * search that did not take that path.  The host knows the figures: this call
+ * waits for nothing. */
+uint64_t rure_amd_last_lazy_long(uint64_t *haystacks, uint64_t *chunk, uint32_t *rounds, uint32_t *fell_back);
 /* Debug-only overrides of the engine dispatch and launch geometry
  * (regex_amd/csrc/host/knobs.hpp lists them): replaces the whole override
  * table, read once per process from RURE_AMD_DEBUG, by spec

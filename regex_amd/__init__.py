@@ -905,6 +905,40 @@ class Regex(object):
             _check(rc, "lazy_build")
         return rc == 1
 
+    def lazy_strip(self):
+        """The strip links of the on-demand DFA as they stand: one uint32 per
+        state, the id of its twin without the unanchored prefix's threads
+        (the state a chunked scan of a long haystack steps into at a unit's
+        cut), 0 = dead, 0x7FFFFFFF = not computed yet.  Raises RuntimeError
+        where the regex has no such automaton or is anchored at the start."""
+        import numpy as np
+        _check(N.rure_amd_lazy_strip_export(self._re, None), "lazy_strip_export")
+        info = N.LazyInfo()
+        _check(N.rure_amd_lazy_export(self._re, ctypes.byref(info), None, None, None, None, None), "lazy_export")
+        strip = np.zeros(info.states, dtype=np.uint32)
+        _check(N.rure_amd_lazy_strip_export(self._re, strip.ctypes.data), "lazy_strip_export")
+        return strip
+
+    def lazy_strip_build(self, states):
+        """Makes the strip links of `states` (a new twin is a new state with
+        its row not built); False once the memory budget is spent."""
+        arr = (ctypes.c_uint32 * max(len(states), 1))(*[int(s) for s in states])
+        rc = N.rure_amd_lazy_strip_build(self._re, arr, len(states))
+        if rc < 0:
+            _check(rc, "lazy_strip_build")
+        return rc == 1
+
+    @staticmethod
+    def last_lazy_long():
+        """(units, haystacks, chunk, rounds, fell_back) of the last find /
+        is_match / shortest_match (or captures bounds) call of this process
+        that cut few long haystacks into units on the on-demand DFA; all 0
+        before the first and after a regex search that took another path."""
+        n, c = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        r, f = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        units = N.rure_amd_last_lazy_long(ctypes.byref(n), ctypes.byref(c), ctypes.byref(r), ctypes.byref(f))
+        return int(units), int(n.value), int(c.value), int(r.value), int(f.value)
+
 
 def replace_all_chain(regexes, reps, haystack, length=None, capacity=None, stream=None):
     """replace_all of each regex in turn over one haystack, every step on the

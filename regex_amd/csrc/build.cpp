@@ -865,11 +865,12 @@ LazyDfa *regex_lazy(rure *re) {
 // Its device side: the reverse DFA it finds match starts with (t.r, or drev
 // packed and uploaded here when the forward DFA did not materialise); the
 // table itself is uploaded by the rounds (dispatch.cpp lazy_rounds).
-bool lazy_device(const DevTables &tc) {
+bool lazy_device(const DevTables &tc, bool locked) {
   DevTables &t = const_cast<DevTables &>(tc);
   rure *re = t.owner;
   if (!re) return false;
-  std::lock_guard<std::mutex> g(re->mu);
+  std::unique_lock<std::mutex> g(re->mu, std::defer_lock);
+  if (!locked) g.lock();
   if (t.lazy_tried) return t.has_lazy;
   t.lazy_tried = true;
   if (!regex_lazy_locked(re)) return false;

@@ -76,7 +76,7 @@ bool captures_call(rure *re, const uint8_t *hay, size_t len, size_t start, uint6
   Scratch<uint64_t> wide;  // more slots than the staging area's result holds
   if (ns > 64 && !hip_ok(wide.alloc((size_t)ns * 8, st), &err)) die(err);
   uint64_t *dev = wide ? wide.get() : re->stage.res;
-  if (!hip_ok(run_captures(b, *t, dev, ns, st, 1), &err)) die(err);
+  if (!hip_ok(run_captures(b, *t, dev, ns, st, 1, true), &err)) die(err);
   if (!hip_ok(hipMemcpyAsync(slots, dev, (size_t)ns * 8, hipMemcpyDeviceToHost, st), &err)) die(err);
   if (!hip_ok(hipStreamSynchronize(st), &err)) die(err);
   if (slots[0] == kQuit || slots[1] == kQuit) die("internal error: unresolved DFA quit");
@@ -1048,6 +1048,27 @@ int rure_amd_lazy_build(rure *re, const uint32_t *states, size_t n, size_t ahead
   return L->expand(ahead) ? 1 : 0;
 }
 
+int rure_amd_lazy_strip_export(rure *re, uint32_t *strip) {
+  if (!re) return RURE_AMD_ERR_ARG;
+  LazyDfa *L = regex_lazy(re);
+  if (!L || !L->has_strip()) return RURE_AMD_ERR_DFA;
+  std::lock_guard<std::mutex> g(re->mu);
+  if (strip) memcpy(strip, L->strip.data(), L->strip.size() * 4);
+  return RURE_AMD_OK;
+}
+
+int rure_amd_lazy_strip_build(rure *re, const uint32_t *states, size_t n) {
+  if (!re || (!states && n)) return RURE_AMD_ERR_ARG;
+  LazyDfa *L = regex_lazy(re);
+  if (!L || !L->has_strip()) return RURE_AMD_ERR_DFA;
+  std::lock_guard<std::mutex> g(re->mu);
+  for (size_t i = 0; i < n; ++i) {
+    if (states[i] >= L->nstates()) return RURE_AMD_ERR_ARG;
+    if (!L->strip_of(states[i])) return 0;
+  }
+  return 1;
+}
+
 int rure_amd_set_core_export(rure_set *rs, rure_amd_core_info *info, uint8_t *lds, uint16_t *gcore,
                              uint64_t *gout, uint64_t *eof, uint16_t *start) {
   if (!rs || rs->single || rs->exprs.size() < 2) return RURE_AMD_ERR_ARG;
@@ -1221,6 +1242,9 @@ uint64_t rure_amd_last_long_units(uint64_t *haystacks, uint64_t *chunk) {
 }
 uint64_t rure_amd_last_set_units(uint64_t *haystacks, uint64_t *chunk) {
   return rure_amd::last_set_units(haystacks, chunk);
+}
+uint64_t rure_amd_last_lazy_long(uint64_t *haystacks, uint64_t *chunk, uint32_t *rounds, uint32_t *fell_back) {
+  return rure_amd::last_lazy_long(haystacks, chunk, rounds, fell_back);
 }
 int rure_amd_suffix_forward(rure *re) {
   if (!re) return RURE_AMD_ERR_ARG;

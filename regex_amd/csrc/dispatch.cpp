@@ -41,6 +41,26 @@ void note_set_units(uint64_t units, uint64_t haystacks, uint64_t chunk) {
   g_set_units[2] = chunk;
 }
 
+// rure_amd_last_lazy_long: likewise (units, haystacks, chunk, rounds, fell back).
+static std::mutex g_lazy_long_mu;
+static uint64_t g_lazy_long[5] = {0, 0, 0, 0, 0};
+uint64_t last_lazy_long(uint64_t *haystacks, uint64_t *chunk, uint32_t *rounds, uint32_t *fell_back) {
+  std::lock_guard<std::mutex> g(g_lazy_long_mu);
+  if (haystacks) *haystacks = g_lazy_long[1];
+  if (chunk) *chunk = g_lazy_long[2];
+  if (rounds) *rounds = (uint32_t)g_lazy_long[3];
+  if (fell_back) *fell_back = (uint32_t)g_lazy_long[4];
+  return g_lazy_long[0];
+}
+static std::atomic<bool> g_lazy_long_any{false};  // the record is not all 0
+static void note_lazy_long(uint64_t units, uint64_t haystacks, uint64_t chunk, uint32_t rounds, bool fell_back) {
+  if (!units && !g_lazy_long_any.load(std::memory_order_relaxed)) return;  // (nothing to clear: no lock per search)
+  std::lock_guard<std::mutex> g(g_lazy_long_mu);
+  g_lazy_long_any.store(units != 0, std::memory_order_relaxed);
+  const uint64_t v[5] = {units, haystacks, chunk, rounds, fell_back ? 1u : 0u};
+  memcpy(g_lazy_long, v, sizeof(v));
+}
+
 // rure_amd_last_long_units: the deferred long scan's figures (haystacks,
 // chunk, units) are made on the device, so its geometry kernel writes them
 // into one pinned record of the process and each call records an event behind
@@ -304,10 +324,16 @@ static bool big_batch(const BatchDev &b, const DevTables &t) {
 // here a spent memory budget or kLazyRounds rounds do the same for the batch:
 // *ok is then false and the caller runs the Pike VM over the whole batch
 // (the rounds' scratch is freed by then).  *rounds = the rounds launched.
-// Park is the kernel's record of a parked lane (LazyPark, LazyIterPark): the
-// rounds read its state `s` and hand the records back to the next launch.
+// Park is the kernel's record of a parked lane (LazyPark, LazyIterPark,
+// LazyLongPark): the rounds read its state `s` and hand the records back to
+// the next launch.  A chunked scan's lane may also park at its unit's cut for
+// the link of `s` (wants_link): the host makes it (LazyDfa::strip_of) and
+// builds the twin's row ahead, and the table carries the links from then on.
 // The caller holds the lock of L's owner.
 constexpr int kLazyRounds = 256;
+static bool wants_link(const LazyPark &) { return false; }
+static bool wants_link(const LazyIterPark &) { return false; }
+static bool wants_link(const LazyLongPark &x) { return x.phase == kLazyLongAtCut; }
 template <class Park, class Launch>
 static hipError_t lazy_rounds(LazyDfa &L, DevTables &t, uint64_t count, hipStream_t st, bool *ok_out, uint32_t *rounds,
                               Launch launch) {
@@ -327,10 +353,11 @@ static hipError_t lazy_rounds(LazyDfa &L, DevTables &t, uint64_t count, hipStrea
   uint64_t nin = 0;
   std::vector<Park> host;
   for (int round = 0; ok && e == hipSuccess; ++round) {
-    // the table: [colmap 256][start 512][now cap * 8][eof_mask cap * 8][eof cap][trans cap * ncol * 4]
-    // (now and eof_mask: a set's, 8-byte aligned; none for a regex)
-    const size_t ns = L.nstates(), nm = L.is_set ? ns : 0;
-    const size_t need = 768 + nm * 16 + ns + ns * (size_t)L.ncol * 4 + 16;
+    // the table: [colmap 256][start 512][now cap * 8][eof_mask cap * 8][eof cap][trans cap * ncol * 4][strip cap * 4]
+    // (now and eof_mask: a set's, 8-byte aligned; none for a regex.  strip:
+    // once a chunked call has made a link)
+    const size_t ns = L.nstates(), nm = L.is_set ? ns : 0, nl = L.nlinks() ? ns : 0;
+    const size_t need = 768 + nm * 16 + ns + ns * (size_t)L.ncol * 4 + nl * 4 + 16;
     if (need > t.lazy_cap) {
       if ((e = hipStreamSynchronize(st)) != hipSuccess) break;
       if (t.lazy_buf) (void)hipFree(t.lazy_buf);
@@ -341,10 +368,11 @@ static hipError_t lazy_rounds(LazyDfa &L, DevTables &t, uint64_t count, hipStrea
     }
     uint8_t *base = (uint8_t *)t.lazy_buf;
     const size_t o_now = 768, o_mask = o_now + nm * 8, o_eof = o_mask + nm * 8, o_trans = (o_eof + ns + 15) & ~(size_t)15;
-    // Uploaded unless the device copy is this very table: states and rows
-    // only ever grow, so their counts name its contents.  A call over text
+    const size_t o_strip = o_trans + ns * (size_t)L.ncol * 4;
+    // Uploaded unless the device copy is this very table: states, rows and
+    // links only ever grow, so their counts name its contents.  A call over text
     // whose rows exist copies nothing (1.4 M states are 186 MB).
-    if (t.lazy_up_states != ns || t.lazy_up_built != L.nbuilt()) {
+    if (t.lazy_up_states != ns || t.lazy_up_built != L.nbuilt() || t.lazy_up_links != L.nlinks()) {
       t.lazy_up_states = 0;
       const auto up = [&](size_t off, const void *src, size_t bytes) {
         return bytes ? hipMemcpyAsync(base + off, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
@@ -352,10 +380,12 @@ static hipError_t lazy_rounds(LazyDfa &L, DevTables &t, uint64_t count, hipStrea
       if ((e = up(0, L.colmap, 256)) != hipSuccess || (e = up(256, L.start, 512)) != hipSuccess ||
           (e = up(o_now, L.now.data(), nm * 8)) != hipSuccess ||
           (e = up(o_mask, L.eof_mask.data(), nm * 8)) != hipSuccess || (e = up(o_eof, L.eof.data(), ns)) != hipSuccess ||
-          (e = up(o_trans, L.trans.data(), L.trans.size() * 4)) != hipSuccess)
+          (e = up(o_trans, L.trans.data(), L.trans.size() * 4)) != hipSuccess ||
+          (e = up(o_strip, L.strip.data(), nl * 4)) != hipSuccess)
         break;
       t.lazy_up_states = ns;
       t.lazy_up_built = L.nbuilt();
+      t.lazy_up_links = L.nlinks();
     }
     LazyDfaDev f{};
     f.colmap = base;
@@ -364,6 +394,7 @@ static hipError_t lazy_rounds(LazyDfa &L, DevTables &t, uint64_t count, hipStrea
     f.eof_mask = nm ? (const uint64_t *)(base + o_mask) : nullptr;
     f.eof = base + o_eof;
     f.trans = (const uint32_t *)(base + o_trans);
+    f.strip = nl ? (const uint32_t *)(base + o_strip) : nullptr;
     f.ncol = L.ncol;
     f.hot = std::min<uint32_t>((uint32_t)ns, lazy_dfa_hot_rows(L.ncol));
     Park *po = pk[round & 1].get();
@@ -379,8 +410,11 @@ static hipError_t lazy_rounds(LazyDfa &L, DevTables &t, uint64_t count, hipStrea
     if ((e = hipMemcpyAsync(host.data(), po, n * sizeof(Park), hipMemcpyDeviceToHost, st)) != hipSuccess ||
         (e = hipStreamSynchronize(st)) != hipSuccess)
       break;
-    for (const Park &x : host)
-      if (!(ok = L.build_row(x.s))) break;
+    for (const Park &x : host) {
+      if (!wants_link(x)) ok = L.build_row(x.s);
+      else if (x.s < L.nstates() && (ok = L.strip_of(x.s))) ok = L.build_row(L.strip[x.s]);
+      if (!ok) break;
+    }
     // (a fixed number ahead: doubling the rows built ahead each round built
     // states in discovery order the text never visits, seconds of host work
     // for (?:a|b)*a(?:a|b){20})
@@ -417,6 +451,68 @@ static bool lazy_batch(const BatchDev &b, const DevTables &t) {
   const bool force = knob(Knob::Lazy) == 1;
   if (!force && (t.has_dfa || !big_batch(b, t))) return false;
   return lazy_device(t);
+}
+
+// Few long fixed-stride haystacks (a log buffer, one document) of such a
+// regex: one lane per haystack would walk each alone and the Pike VM gives
+// one a wave, so the search is cut into units as long_batch cuts it for a
+// regex with an eager DFA (its span and count thresholds, its chunk rule) and
+// the units run on the on-demand DFA (run_lazy_long).  Not for batches that
+// fill the device (big_batch: one lane per haystack), offset batches, nor a
+// program anchored at the start (no `.*?` prefix, so no links: its lanes die
+// where the text stops matching).  Knobs lazy_long: 0 never, 2 at any length
+// and count (tests); lazy_chunk: the unit size in bytes.  locked: the caller
+// holds the lock of t's owner (the single-haystack calls).
+static bool lazy_long_batch(const BatchDev &b, const DevTables &t, bool locked, uint64_t *chunk) {
+  const long long mode = knob(Knob::LazyLong);
+  if (mode == 0 || knob(Knob::Lazy) == 0 || b.offs || b.count == 0 || !t.owner) return false;
+  if (t.has_dfa && knob(Knob::Lazy) != 1) return false;
+  const uint64_t span = b.length > b.start ? b.length - b.start : 0;
+  if (mode != 2 && (big_batch(b, t) || span < kLongSpan || b.count >= (uint64_t)t.cus * 128)) return false;
+  if (t.owner->fwd.dotstar_end == 0) return false;  // anchored at the start (before any automaton is made for it)
+  if (!lazy_device(t, locked) || !t.owner->lazy->has_strip()) return false;
+  *chunk = unit_bytes(span, b.count, lanes_in_flight(t.cus, Knob::LongLanes), kLongFloor);
+  if (knob(Knob::LazyChunk) > 0) *chunk = std::max<uint64_t>(16, knob(Knob::LazyChunk));
+  return true;
+}
+
+// Rounds of lazy_long_kernel over the units until none is parked, then (find)
+// the finish step.  Synchronous, as run_lazy; a spent budget or kLazyRounds
+// rounds send the whole batch to the Pike VM.
+static hipError_t run_lazy_long(int mode, const BatchDev &b, const DevTables &tc, uint64_t chunk, void *out,
+                                hipStream_t st, bool locked) {
+  DevTables &t = const_cast<DevTables &>(tc);
+  rure *re = t.owner;
+  std::unique_lock<std::mutex> g(re->mu, std::defer_lock);
+  if (!locked) g.lock();
+  const uint64_t units = lazy_long_units(b, chunk);
+  const auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  Scratch<uint8_t> buf;
+  uint64_t *ures = nullptr;
+  unsigned long long *best = (unsigned long long *)out;  // is_match / shortest_match: the output itself
+  hipError_t e;
+  if (mode == MODE_FIND) {
+    if ((e = buf.alloc(al(units * 8) + al(b.count * 8), st)) != hipSuccess) return e;
+    ures = (uint64_t *)buf.get();
+    best = (unsigned long long *)(buf.get() + al(units * 8));
+    e = hipMemsetAsync(best, 0xFF, b.count * 8, st);
+  } else {
+    e = hipMemsetAsync(out, mode == MODE_ISMATCH ? 0 : 0xFF, b.count * (mode == MODE_ISMATCH ? 1 : 8), st);
+  }
+  if (e != hipSuccess) return e;
+  bool ok = true;
+  uint32_t rounds = 0;
+  e = lazy_rounds<LazyLongPark>(*re->lazy, t, units, st, &ok, &rounds,
+                                [&](const LazyDfaDev &f, const LazyLongPark *in, uint64_t nin, LazyLongPark *po,
+                                    unsigned long long *cnt) {
+                                  return launch_lazy_long(mode, b, f, chunk, in, nin, po, cnt, ures, best, st, t.cus);
+                                });
+  if (e == hipSuccess && ok && mode == MODE_FIND)
+    e = launch_lazy_long_finish(b, t.lr, ures, best, (uint64_t *)out, st, t.cus);
+  buf.reset();
+  note_lazy_long(units, b.count, chunk, rounds, e == hipSuccess && !ok);
+  if (e != hipSuccess || ok) return e;
+  return run_pike(mode, false, b, t, out, st);  // the whole batch again
 }
 
 // The batched find_iter on the on-demand forward DFA (lazy_batch's regexes):
@@ -532,8 +628,12 @@ static hipError_t run_lit_find(int mode, rure *re, const BatchDev &b, const DevT
   return launch_lit_find(mode, b, lit, out, st);
 }
 
+// locked: the caller holds the lock of t's owner (the single-haystack calls).
 static hipError_t run_regex(int mode, const BatchDev &b, const DevTables &t, void *out, hipStream_t st, int dfa_grid,
-                            const FwdDfaDev *iter = nullptr) {
+                            const FwdDfaDev *iter = nullptr, bool locked = false) {
+  uint64_t lchunk = 0;
+  if (!lane_search_ok(t) && lazy_long_batch(b, t, locked, &lchunk)) return run_lazy_long(mode, b, t, lchunk, out, st, locked);
+  note_lazy_long(0, 0, 0, 0, false);
   if (lane_search_ok(t)) return run_lane_search(mode, b, t, out, st);
   if (knob(Knob::Lazy) == 1 && lazy_batch(b, t))
     return run_lazy(mode, b, t, out, st);
@@ -642,16 +742,22 @@ static hipError_t caps_grid(size_t units, const DevTables &t, uint32_t ns, hipSt
 // the text up to two characters past the match end, or over the whole
 // haystack where the DFA quit and for anchored-start programs.  A regex whose
 // DFA does not materialise takes its bounds from the on-demand DFA on batches
-// that fill the device (lazy_batch; the reference's lazy DFA produces them),
-// else from the Pike VM.
+// that fill the device (lazy_batch; the reference's lazy DFA produces them)
+// and on few long haystacks (lazy_long_batch: the captures Pike VM then runs
+// over the match window of a long text, not over all of it), else from the
+// Pike VM.  locked: the caller holds the lock of t's owner.
 hipError_t run_captures(const BatchDev &b, const DevTables &t, uint64_t *slots, uint32_t ns, hipStream_t st,
-                        int dfa_grid) {
-  if (ns <= 2) return run_regex(MODE_FIND, b, t, slots, st, dfa_grid);
+                        int dfa_grid, bool locked) {
+  if (ns <= 2) return run_regex(MODE_FIND, b, t, slots, st, dfa_grid, nullptr, locked);
   hipError_t e = hipSuccess;
   Scratch<uint64_t> found;
   if (!t.n.anchored) {
     if ((e = found.alloc(b.count * 16, st)) != hipSuccess) return e;
+    uint64_t lchunk = 0;
+    const bool chunked = !lane_search_ok(t) && lazy_long_batch(b, t, locked, &lchunk);
+    if (!chunked) note_lazy_long(0, 0, 0, 0, false);
     e = lane_search_ok(t) ? launch_lane_search(MODE_FIND, b, t.m, t.f, t.r, found.get(), st, t.cus)
+        : chunked         ? run_lazy_long(MODE_FIND, b, t, lchunk, found.get(), st, locked)
         : t.has_dfa       ? run_dfa_step(MODE_FIND, b, t, found.get(), st, dfa_grid, nullptr)
         : lazy_batch(b, t) ? run_lazy(MODE_FIND, b, t, found.get(), st)
                            : run_pike(MODE_FIND, false, b, t, found.get(), st);
@@ -711,7 +817,7 @@ bool single_call(rure *re, int mode, const uint8_t *hay, size_t len, size_t star
   hipStream_t st = re->stage.stream;
   if (len && !hip_ok(hipMemcpyAsync(re->stage.hay, hay, len, hipMemcpyHostToDevice, st), &err)) die(err);
   BatchDev b{re->stage.hay, nullptr, len, len, 1, start};
-  if (!hip_ok(run_regex(mode, b, *t, re->stage.res, st, 1, iter), &err)) die(err);
+  if (!hip_ok(run_regex(mode, b, *t, re->stage.res, st, 1, iter, true), &err)) die(err);
   uint64_t out[2] = {~0ull, ~0ull};
   size_t nbytes = mode == MODE_FIND ? 16 : mode == MODE_SHORTEST ? 8 : 1;
   if (!hip_ok(hipMemcpyAsync(out, re->stage.res, nbytes, hipMemcpyDeviceToHost, st), &err)) die(err);
@@ -789,6 +895,7 @@ int search_batch(int mode, rure *re, const rure_amd_batch *batch, void *out, hip
   BatchDev b;
   if (!re || !to_batch(batch, &b) || (!out && b.count)) return RURE_AMD_ERR_ARG;
   if (b.count == 0) return RURE_AMD_OK;
+  note_lazy_long(0, 0, 0, 0, false);  // (run_lazy_long writes it)
   std::string err;
   DevTables *t = regex_device(re, &err);
   if (!t) return err.rfind("HIP", 0) == 0 ? RURE_AMD_ERR_HIP : RURE_AMD_ERR_DFA;

@@ -85,6 +85,15 @@ class Builder {
     return m;
   }
   uint32_t lazy_start(int fi) const { return start_used_[fi] ? start_raw_[fi] : 0; }
+  // The twin of raw state s without the `.*?` prefix threads (strip_key),
+  // interned after every state there is when it is new; 0 = dead.  A program
+  // anchored at the start has no prefix and no twins.
+  bool lazy_has_prefix() const { return p_.dotstar_end > 0; }
+  uint32_t lazy_strip(uint32_t s) {
+    if (s < 2) return s;
+    const std::string key = keys_[s];  // copy: keys_ may grow
+    return strip_key(key);
+  }
 
   bool build(DenseDfa *out, std::string *err) {
     const auto t_begin = std::chrono::steady_clock::now();
@@ -736,6 +745,7 @@ void LazyDfa::sync_new() {
       eof_mask.push_back(impl_->b.lazy_eof_mask(s));
     }
     built.push_back(s < 2 ? 1 : 0);
+    strip.push_back(s < 2 ? s : kLazyUnknown);
     trans.resize((size_t)(s + 1) * ncol, s < 2 ? s : kLazyUnknown);
     if (s >= 2) todo_.push_back(s);
   }
@@ -750,6 +760,21 @@ bool LazyDfa::build_row(uint32_t s) {
   for (uint32_t c = 0; c < ncol; ++c) trans[(size_t)s * ncol + c] = entry_of(row[c]);
   built[s] = 1;
   ++nbuilt_;
+  return true;
+}
+
+bool LazyDfa::has_strip() const { return impl_->b.lazy_has_prefix(); }
+
+// The link of state s for a chunked scan's cut: its twin is interned (a new
+// state: numbered after all others, its row unknown), and is its own twin.
+bool LazyDfa::strip_of(uint32_t s) {
+  if (s >= strip.size() || strip[s] != kLazyUnknown) return true;
+  if (max_bytes_ && impl_->b.lazy_bytes() + trans.size() * 4 + now.size() * 16 > max_bytes_) return false;
+  const uint32_t t = impl_->b.lazy_strip(s);
+  sync_new();
+  strip[s] = t;
+  strip[t] = t;
+  ++nlinks_;
   return true;
 }
 

@@ -100,21 +100,31 @@ class LazyDfa {
   bool build_row(uint32_t s);
   // Builds up to `rows` more rows in discovery order.
   bool expand(size_t rows);
+  // Sets strip[s]: the twin of s without the `.*?` prefix threads, which a
+  // chunked scan steps into at a unit's cut (DenseDfa::strip, on demand).  A
+  // new twin is numbered after every existing state, with its row unknown, and
+  // is its own twin.  No state, row or flag there was changes.  False: the
+  // memory budget is spent.  Only where has_strip().
+  bool strip_of(uint32_t s);
+  // The program has a `.*?` prefix (it is not anchored at the start).
+  bool has_strip() const;
   uint32_t nstates() const { return (uint32_t)eof.size(); }
   size_t nbuilt() const { return nbuilt_; }
+  size_t nlinks() const { return nlinks_; }
   uint32_t ncol = 0;
   uint8_t colmap[256] = {0};
   uint32_t start[128];            // entries (id | kLazyMatch) per start-flag index
   std::vector<uint32_t> trans;    // nstates * ncol entries
   std::vector<uint8_t> eof;       // per state: the EOF step yields a match
   std::vector<uint8_t> built;     // per state: its row is built
+  std::vector<uint32_t> strip;    // per state: its twin's id (no match bit), 0 = dead, kLazyUnknown until strip_of
   bool is_set = false;            // a set program: now / eof_mask per state (else empty)
   std::vector<uint64_t> now;      // Match slots reported by the step into the state
   std::vector<uint64_t> eof_mask; // Match slots the EOF step from the state reaches
  private:
   struct Impl;
   Impl *impl_ = nullptr;
-  size_t max_bytes_ = 0, nbuilt_ = 0;
+  size_t max_bytes_ = 0, nbuilt_ = 0, nlinks_ = 0;
   std::vector<uint32_t> todo_;
   size_t todo_head_ = 0;
   uint32_t entry_of(uint32_t s) const;

@@ -51,6 +51,8 @@ enum class Knob : int {
   LongList,        // the capacity of its list of deferred haystacks
   SetLong,         // 0: a RegexSet's long haystacks one lane each; 2: chunked at any length and count
   SetChunk,        // the unit size in bytes of the chunked RegexSet scan (floor 16)
+  LazyLong,        // 0: few long haystacks of a regex past the eager budgets keep the Pike VM; 2: chunked on the on-demand DFA at any length and count
+  LazyChunk,       // the unit size in bytes of that chunked scan (floor 16, no odd-lines rounding)
   kCount
 };
 

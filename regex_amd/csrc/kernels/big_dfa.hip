@@ -9,16 +9,18 @@
 // builds such automata lazily in a bounded cache; the host materialises them
 // eagerly (dfa_build.cpp, column form) so a lane only reads tables.  Past
 // that budget too, rows are built on demand between rounds of
-// lazy_dfa_kernel (a regex), lazy_iter_kernel (its find_iter) or
-// lazy_set_kernel (a RegexSet's matches).
+// lazy_dfa_kernel (a regex), lazy_long_kernel (its few long haystacks, cut
+// into units), lazy_iter_kernel (its find_iter) or lazy_set_kernel (a
+// RegexSet's matches).
 //
-// Execution: one lane per haystack.  A 16-byte chunk's columns come from the
+// Execution: one lane per haystack (lazy_long_kernel: per unit).  A 16-byte chunk's columns come from the
 // LDS column map first (independent of the state), then the dependent chain
 // is one table read per byte: LDS for hot states, global otherwise.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "dfa_device.hpp"
+#include "iter_device.hpp"
 
 namespace rure_amd {
 namespace {
@@ -493,7 +495,221 @@ __global__ __launch_bounds__(1024) void lazy_set_kernel(BatchDev bt, LazyDfaDev 
   }
 }
 
+// Few long fixed-stride haystacks on the on-demand DFA: the cut-bounded
+// search of long_scan.hip's long_unit, one lane per unit, with the walk,
+// staging and match bookkeeping of lazy_dfa_kernel.  Unit [c0, c1) takes the
+// start state at c0, walks through c1 - 1 (phase kLazyLongBefore), steps into
+// strip[s] there (kLazyLongAtCut: the threads started in the unit alone go
+// on) and walks until the automaton dies or the text ends (kLazyLongAfter);
+// the unit that owns the end has no cut and is in the last phase from its
+// start.  A lane parks on a row not built yet, or at the cut on a link not
+// computed, and a later round resumes it in the phase it was in.
+//
+// Results as long_scan_m gathers them: is_match stores a byte, shortest_match
+// takes the minimum end (best = the output for both), find keeps the unit's
+// match end in ures[u] and the smallest matching unit in best[h]; the match's
+// start is found once, for the winner (lazy_long_finish_kernel).  Once per
+// 512 bytes of text a lane reads what its haystack has published and leaves
+// when it cannot change it (a load outside the per-byte chain).
+template <int MODE>
+__device__ __forceinline__ void lazy_long_publish(unsigned long long *best, uint64_t *ures, uint64_t h, uint64_t u,
+                                                  uint64_t last) {
+  if (last == NONE) return;
+  if (MODE == MODE_ISMATCH) {
+    ((uint8_t *)best)[h] = 1;
+  } else if (MODE == MODE_SHORTEST) {
+    atomicMin(&best[h], (unsigned long long)last);
+  } else {
+    ures[u] = last;
+    atomicMin(&best[h], (unsigned long long)u);
+  }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(1024) void lazy_long_kernel(BatchDev bt, Geo g, uint64_t nunits, LazyDfaDev f,
+                                                         const LazyLongPark *in, uint64_t nin, LazyLongPark *park,
+                                                         unsigned long long *npark, uint64_t *ures,
+                                                         unsigned long long *best) {
+  __shared__ __attribute__((aligned(16))) uint32_t hot_rows[kBigLdsBytes / 4];
+  __shared__ uint8_t colmap[256];
+  const uint32_t nhot = f.hot * f.ncol;
+  for (uint32_t i = threadIdx.x; i < nhot; i += blockDim.x) hot_rows[i] = f.trans[i];
+  for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x) colmap[i] = f.colmap[i];
+  __syncthreads();
+  const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x, nl = in ? nin : nunits;
+  for (uint64_t l = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; l < nl; l += nthreads) {
+    const uint64_t u = in ? in[l].u : l;
+    uint64_t h, len, c0, c1;
+    const uint8_t *base;
+    unit_bounds<false>(bt, g, u, &h, &base, &len, &c0, &c1);
+    const bool cut = c1 > c0 && c1 - 1 <= len;  // as long_unit
+    uint64_t last = NONE, p = c0;
+    uint32_t s = 0, phase = cut ? kLazyLongBefore : kLazyLongAfter;
+    bool done = c0 > len, parked = false;
+    uintptr_t nblk = 0;  // the block `nxt` holds (0: none)
+    uint4 nxt = make_uint4(0, 0, 0, 0);
+    if (in) {
+      p = in[l].p;
+      last = in[l].last;
+      s = in[l].s;
+      phase = in[l].phase;
+    } else if (!done) {
+      s = f.start[fwd_flag_index(base, len, c0)] & ~kLazyMatchBit;
+      done = s == 0;  // dead start state (dfa.rs:484)
+    }
+    while (!done) {
+      if (phase == kLazyLongAtCut) {
+        const uint32_t e = f.strip ? f.strip[s] : kLazyUnknownEntry;
+        if (e == kLazyUnknownEntry) {
+          parked = true;
+          break;
+        }
+        if (e == 0) {
+          done = true;  // no thread started in the unit is alive
+          lazy_long_publish<MODE>(best, ures, h, u, last);
+          break;
+        }
+        s = e;
+        phase = kLazyLongAfter;
+      }
+      const uint64_t lim = phase == kLazyLongBefore ? c1 - 1 : len;
+      while (!done && !parked && p < lim) {
+        const uintptr_t a = (uintptr_t)(base + p), blk = a & ~(uintptr_t)15;
+        if ((a & 0x1F0) == 0) {  // what the haystack has published so far
+          bool leave;
+          if (MODE == MODE_ISMATCH) {
+            leave = __hip_atomic_load((const uint8_t *)best + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+          } else {
+            const unsigned long long v = __hip_atomic_load(&best[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            // shortest_match: an end at or before c0 (this unit's are later); find: a smaller unit
+            leave = MODE == MODE_SHORTEST ? v <= c0 : v < u;
+          }
+          if (leave) {
+            last = NONE;
+            done = true;
+            break;
+          }
+        }
+        // this block (loaded a pass ago when the walk came here in order),
+        // and the next one's load in flight while this one's bytes are stepped
+        const uint4 v = blk == nblk ? nxt : *(const uint4 *)blk;
+        if (blk + 16 < (uintptr_t)(base + len)) {
+          nblk = blk + 16;
+          nxt = *(const uint4 *)nblk;
+        }
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+        const uint32_t j0 = (uint32_t)(a & 15);
+        const uint32_t n = (uint32_t)min<uint64_t>(16 - j0, lim - p);
+        uint32_t j = j0;
+        for (; j < j0 + n; ++j) {
+          const uint32_t c = colmap[(w[j >> 2] >> (8 * (j & 3))) & 0xFF];
+          const uint32_t e = s < f.hot ? hot_rows[s * f.ncol + c] : f.trans[(size_t)s * f.ncol + c];
+          if (e == kLazyUnknownEntry) {
+            parked = true;
+            break;
+          }
+          if (e == 0) {
+            done = true;  // dead
+            break;
+          }
+          s = e & ~kLazyMatchBit;
+          if (e & kLazyMatchBit) {  // dfa.rs:658-668: Match(at - 1)
+            last = p + (j - j0);
+            if (MODE != MODE_FIND) {
+              done = true;  // quit_after_match
+              break;
+            }
+          }
+        }
+        p += j - j0;
+        // A finished unit publishes here, inside the walk: after the loop the
+        // wave's lanes meet again only when its slowest one is through, and
+        // the units that could leave on this result would walk on until then.
+        if (done) lazy_long_publish<MODE>(best, ures, h, u, last);
+      }
+      if (done || parked || phase == kLazyLongAfter) break;
+      phase = kLazyLongAtCut;
+    }
+    if (parked) {
+      const unsigned long long k = atomicAdd(npark, 1ull);
+      LazyLongPark x;
+      x.u = u;
+      x.p = p;
+      x.last = last;
+      x.s = s;
+      x.phase = phase;
+      park[k] = x;
+      continue;
+    }
+    if (done) continue;  // (published where it finished)
+    if (f.eof[s]) last = len;  // dfa.rs:748-763
+    lazy_long_publish<MODE>(best, ures, h, u, last);
+  }
+}
+
+// find: the winner's match (find_dfa_forward, exec.rs:632-662): its end from
+// the smallest unit that matched, its start from the reverse DFA over
+// text[start..end]; an empty match at `start` starts there (exec.rs:647), a
+// reverse NoMatch makes the search's answer "no match" (exec.rs:656-660).
+__global__ __launch_bounds__(256) void lazy_long_finish_kernel(BatchDev bt, RevDfaDev r, const uint64_t *ures,
+                                                               const unsigned long long *best, uint64_t *out) {
+  for (uint64_t h = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; h < bt.count; h += (uint64_t)gridDim.x * blockDim.x) {
+    const unsigned long long v = best[h];
+    uint64_t ms = NONE, me = NONE;
+    if (v != ~0ull) {
+      me = ures[v];
+      if (me == bt.start) {
+        ms = me;
+      } else {
+        ms = rev_scan(r, nullptr, bt.hay + h * bt.stride, bt.length, bt.start, me);
+        if (ms == NONE) me = NONE;
+      }
+    }
+    out[2 * h] = ms;
+    out[2 * h + 1] = me;
+  }
+}
+
+template <int MODE>
+hipError_t launch_lazy_long_m(const BatchDev &b, const Geo &g, uint64_t nunits, const LazyDfaDev &f,
+                              const LazyLongPark *in, uint64_t nin, LazyLongPark *park, unsigned long long *npark,
+                              uint64_t *ures, unsigned long long *best, hipStream_t st, int cus) {
+  const uint64_t lanes = in ? nin : nunits;
+  const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>((lanes + 1023) / 1024, (uint64_t)cus * 2));
+  hipLaunchKernelGGL((lazy_long_kernel<MODE>), dim3(grid), dim3(1024), 0, st, b, g, nunits, f, in, nin, park, npark,
+                     ures, best);
+  return hipGetLastError();
+}
+
 }  // namespace
+
+hipError_t launch_lazy_long(int mode, const BatchDev &b, const LazyDfaDev &f, uint64_t chunk, const LazyLongPark *in,
+                            uint64_t nin, LazyLongPark *park, unsigned long long *npark, uint64_t *ures,
+                            unsigned long long *best, hipStream_t st, int cus) {
+  if (b.offs || chunk == 0) return hipErrorInvalidValue;
+  if (b.count == 0 || (in && nin == 0)) return hipSuccess;
+  note_fwd_path(RURE_AMD_PATH_LAZY_DFA);
+  Geo g;  // long_scan_m's
+  g.chunk = chunk;
+  g.end = ~0ull;
+  g.slots = 0;
+  const uint64_t nunits = lazy_long_units(b, chunk);
+  g.nk = nunits / b.count;
+  switch (mode) {
+    case MODE_FIND: return launch_lazy_long_m<MODE_FIND>(b, g, nunits, f, in, nin, park, npark, ures, best, st, cus);
+    case MODE_ISMATCH:
+      return launch_lazy_long_m<MODE_ISMATCH>(b, g, nunits, f, in, nin, park, npark, ures, best, st, cus);
+    default: return launch_lazy_long_m<MODE_SHORTEST>(b, g, nunits, f, in, nin, park, npark, ures, best, st, cus);
+  }
+}
+
+hipError_t launch_lazy_long_finish(const BatchDev &b, const RevDfaDev &r, const uint64_t *ures,
+                                   const unsigned long long *best, uint64_t *out, hipStream_t st, int cus) {
+  if (b.count == 0) return hipSuccess;
+  hipLaunchKernelGGL(lazy_long_finish_kernel, dim3(grid_cap(b.count, 256, cus, 4)), dim3(256), 0, st, b, r, ures, best,
+                     out);
+  return hipGetLastError();
+}
 
 hipError_t launch_lazy_set(const BatchDev &b, const LazyDfaDev &f, uint64_t all, const LazyPark *in, uint64_t nin,
                            LazyPark *park, unsigned long long *npark, uint64_t *out, hipStream_t st, int cus) {

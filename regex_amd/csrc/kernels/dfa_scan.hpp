@@ -564,6 +564,10 @@ void note_iter_units(uint64_t units, uint64_t haystacks);
 // (rure_amd_last_set_units; all 0 after a set call that did not chunk).
 uint64_t last_set_units(uint64_t *haystacks, uint64_t *chunk);
 void note_set_units(uint64_t units, uint64_t haystacks, uint64_t chunk);
+// The units, haystacks, unit size, rounds and whether the Pike VM answered
+// instead, of the last chunked on-demand DFA call (rure_amd_last_lazy_long;
+// all 0 after a regex search that did not take that path).
+uint64_t last_lazy_long(uint64_t *haystacks, uint64_t *chunk, uint32_t *rounds, uint32_t *fell_back);
 // Kernel timer (rure_amd_kernel_timer): HIP event pairs around bracketed launches.
 void ktimer_begin(hipStream_t st);
 void ktimer_end(hipStream_t st);
@@ -625,6 +629,10 @@ struct LazyDfaDev {
   uint32_t ncol, hot;
   const uint64_t *now;        // per state (sets)
   const uint64_t *eof_mask;   // per state (sets)
+  // per state: the twin without the `.*?` prefix threads that a chunked scan
+  // steps into at a unit's cut (an id without the match bit, 0 = dead,
+  // 0x7FFFFFFF = not computed yet); null until a chunked call made a link
+  const uint32_t *strip;
 };
 // A lane stopped at a row not built yet: haystack, position of the byte it
 // needs, the last match end so far (~0: none; a set: the mask collected so
@@ -647,6 +655,35 @@ hipError_t launch_lazy_dfa(int mode, const BatchDev &b, const LazyDfaDev &f, con
 hipError_t launch_lazy_set(const BatchDev &b, const LazyDfaDev &f, uint64_t all, const LazyPark *in, uint64_t nin,
                            LazyPark *park, unsigned long long *npark, uint64_t *out, hipStream_t st, int cus);
 uint32_t lazy_dfa_hot_rows(uint32_t ncol);
+// A unit of the chunked scan on a LazyDfaDev (lazy_long_kernel) stopped: the
+// unit, the position of the byte it needs, its last match end so far (~0:
+// none), the state, and where in the unit's walk it stood.
+enum { kLazyLongBefore = 0, kLazyLongAtCut = 1, kLazyLongAfter = 2 };
+struct LazyLongPark {
+  uint64_t u, p, last;
+  uint32_t s, phase;
+};
+// find / is_match / shortest_match over few long fixed-stride haystacks on a
+// regex's LazyDfaDev, cut into units of `chunk` bytes as launch_long_scan
+// cuts them: unit [c0, c1) walks from c0, steps into strip[state] at c1 - 1
+// and walks on until the automaton dies.  One round: lanes are the units (in
+// = nullptr) or the units parked by the previous round; a unit that needs a
+// missing row, or a link not computed (phase kLazyLongAtCut), is appended to
+// park (*npark).  is_match stores 1 into out[h] and shortest_match takes the
+// minimum into out[h], both initialised by the caller; find keeps the unit's
+// match end in ures[u] and the smallest matching unit in best[h] (initialised
+// to ~0), which launch_lazy_long_finish turns into out after the last round
+// (the reverse DFA r gives the winner's start).
+hipError_t launch_lazy_long(int mode, const BatchDev &b, const LazyDfaDev &f, uint64_t chunk, const LazyLongPark *in,
+                            uint64_t nin, LazyLongPark *park, unsigned long long *npark, uint64_t *ures,
+                            unsigned long long *best, hipStream_t st, int cus);
+hipError_t launch_lazy_long_finish(const BatchDev &b, const RevDfaDev &r, const uint64_t *ures,
+                                   const unsigned long long *best, uint64_t *out, hipStream_t st, int cus);
+// The units per haystack and in all for that geometry.
+inline uint64_t lazy_long_units(const BatchDev &b, uint64_t chunk) {
+  const uint64_t span = b.length > b.start ? b.length - b.start : 0;
+  return b.count * (span <= chunk ? 1 : (span + chunk - 1) / chunk);
+}
 // A find_iter lane stopped at a row not built yet: the haystack, the
 // iteration's state (ip: the start of the search under way, lm: the end of
 // the last match or ~0, count: the matches so far) and that search's (p: the

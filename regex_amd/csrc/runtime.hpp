@@ -92,7 +92,8 @@ struct DevTables {
   bool lazy_tried = false, has_lazy = false;
   void *lazy_buf = nullptr, *lazy_rblob = nullptr;
   size_t lazy_cap = 0;
-  size_t lazy_up_states = 0, lazy_up_built = 0;  // the table lazy_buf holds: its states and built rows (0: none)
+  // the table lazy_buf holds: its states, built rows and strip links (0 states: none)
+  size_t lazy_up_states = 0, lazy_up_built = 0, lazy_up_links = 0;
   RevDfaDev lr{};
   // sets: the strip-built automaton of the chunked long scan (set_long_device),
   // uploaded on the first long call
@@ -361,7 +362,7 @@ bool needs_mt_lane(const ExecLiterals &x);
 void set_prefix_skip(const rure *re, FwdDfaDev *f);
 DevTables *regex_device(rure *re, std::string *err);
 bool big_device(const DevTables &tc);
-bool lazy_device(const DevTables &tc);
+bool lazy_device(const DevTables &tc, bool locked = false);  // locked: the caller holds the owner's lock
 LazyDfa *regex_lazy(rure *re);
 DevTables *set_device(rure_set *rs, std::string *err);
 bool build_set_long(rure_set *rs);
@@ -385,7 +386,7 @@ int grid_for(size_t count, uint32_t lds_bytes, int cus);
 uint64_t lanes_in_flight(int cus, Knob k);
 bool lane_search_ok(const DevTables &t);
 hipError_t run_captures(const BatchDev &b, const DevTables &t, uint64_t *slots, uint32_t ns, hipStream_t st,
-                        int dfa_grid);
+                        int dfa_grid, bool locked = false);  // locked: the caller holds the lock of t's owner
 hipError_t run_captures_iter(const BatchDev &b, const DevTables &t, const IterBufs &ib, uint64_t limit, uint64_t *rows,
                              uint32_t ns, uint8_t *diverged, hipStream_t st);
 bool to_batch(const rure_amd_batch *b, BatchDev *o);
