@@ -6,7 +6,7 @@ LIB = regex_amd/lib/librure_amd.so
 HOST_SRC = regex_amd/csrc/host/syntax.cpp regex_amd/csrc/host/compile.cpp regex_amd/csrc/host/dfa_build.cpp \
            regex_amd/csrc/host/nfa_build.cpp regex_amd/csrc/host/literals.cpp \
            regex_amd/csrc/host/literal_sets.cpp regex_amd/csrc/host/knobs.cpp \
-           regex_amd/csrc/host/expand.cpp
+           regex_amd/csrc/host/expand.cpp regex_amd/csrc/host/tile_skip.cpp
 RT_SRC = regex_amd/csrc/build.cpp regex_amd/csrc/dispatch.cpp regex_amd/csrc/scratch.cpp regex_amd/csrc/capi.cpp
 RT_OBJ = $(patsubst regex_amd/csrc/%.cpp,$(OBJDIR)/rt_%.o,$(RT_SRC))
 KERNEL_SRC = regex_amd/csrc/kernels/dfa_scan.hip regex_amd/csrc/kernels/nfa_scan.hip regex_amd/csrc/kernels/iter_scan.hip \

@@ -717,6 +717,29 @@ uint64_t rure_amd_last_set_units(uint64_t *haystacks, uint64_t *chunk);
  * search that did not take that path.  The host knows the figures: this call
  * waits for nothing. */
 uint64_t rure_amd_last_lazy_long(uint64_t *haystacks, uint64_t *chunk, uint32_t *rounds, uint32_t *fell_back);
+/* The tile kernel's skip rule (host only; kernels/tile_skip_device.hpp): a
+ * regex that is, over ASCII text, one fixed sequence of m byte classes, and
+ * whose packed forward DFA the host proved to leave its hot rows only at a
+ * window of that sequence, lets a wave leave out the walk of a 128-byte tile
+ * in which no lane has a byte >= 0x80 or a window ending.  anchor_a <=
+ * anchor_b: the positions whose byte ranges find the windows (equal: one
+ * anchor; -1: not eligible).  used: the kernel applies the rule, which it
+ * does only where the byte frequency table expects less than one anchor
+ * candidate per wave and tile (verifying more costs more than the walk). */
+typedef struct rure_amd_tile_skip {
+  int32_t eligible;
+  int32_t m;
+  int32_t anchor_a, anchor_b;
+  int32_t used;
+} rure_amd_tile_skip;
+int rure_amd_tile_skip_info(rure *re, rure_amd_tile_skip *info);
+/* One haystack walked the way a lane of the tile kernel walks it under the
+ * skip rule (a wave of one lane, find), and plainly (host only): the forward
+ * DFA state after each whole 128-byte tile both ways (len / 128 entries each)
+ * and whether the lane found the tile dirty.  Returns the number of tiles;
+ * RURE_AMD_ERR_ARG for a regex that is not eligible. */
+int64_t rure_amd_tile_skip_simulate(rure *re, const uint8_t *hay, size_t len, uint32_t *states_skip,
+                                    uint32_t *states_exact, uint8_t *dirty);
 /* Debug-only overrides of the engine dispatch and launch geometry
  * (regex_amd/csrc/host/knobs.hpp lists them): replaces the whole override
  * table, read once per process from RURE_AMD_DEBUG, by spec

@@ -745,6 +745,29 @@ class Regex(object):
         rc = N.rure_amd_dfa_info_get(self._re, which, ctypes.byref(info))
         return {k: getattr(info, k) for k, _ in N.DfaInfo._fields_} if rc == N.OK else None
 
+    def tile_skip_info(self):
+        """The tile kernel's skip rule for this regex (rure_amd_tile_skip_info):
+        {eligible, m, anchor_a, anchor_b, used}, or None without a forward DFA."""
+        info = N.TileSkipInfo()
+        rc = N.rure_amd_tile_skip_info(self._re, ctypes.byref(info))
+        return {k: getattr(info, k) for k, _ in N.TileSkipInfo._fields_} if rc == N.OK else None
+
+    def tile_skip_simulate(self, hay):
+        """One haystack walked as a lane of the tile kernel walks it under the
+        skip rule, and plainly (host only): (states_skip, states_exact, dirty),
+        one entry per whole 128-byte tile; None if the regex is not eligible."""
+        import numpy as np
+        hay = np.ascontiguousarray(np.frombuffer(bytes(hay), dtype=np.uint8))
+        n = len(hay) // 128
+        ss = np.zeros(max(n, 1), dtype=np.uint32)
+        se = np.zeros(max(n, 1), dtype=np.uint32)
+        d = np.zeros(max(n, 1), dtype=np.uint8)
+        rc = N.rure_amd_tile_skip_simulate(self._re, hay.ctypes.data, len(hay), ss.ctypes.data, se.ctypes.data,
+                                           d.ctypes.data)
+        if rc < 0:
+            return None
+        return ss[:n], se[:n], d[:n]
+
     def first_bytes(self):
         """The first-byte start rule of the chunked find_iter (bytes of F, or
         None when the rule does not hold)."""

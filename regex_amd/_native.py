@@ -227,6 +227,12 @@ def last_long_units():
     return int(units), int(n.value), int(c.value)
 
 
+class TileSkipInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("eligible", "m", "anchor_a", "anchor_b", "used")]
+
+
+rure_amd_tile_skip_info = _sig("rure_amd_tile_skip_info", ctypes.c_int, VP, ctypes.POINTER(TileSkipInfo))
+rure_amd_tile_skip_simulate = _sig("rure_amd_tile_skip_simulate", ctypes.c_int64, VP, VP, c_size, VP, VP, VP)
 rure_amd_last_set_units = _sig("rure_amd_last_set_units", ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
                                ctypes.POINTER(ctypes.c_uint64))
 rure_amd_set_long_dfa_export = _sig("rure_amd_set_long_dfa_export", ctypes.c_int, VP, ctypes.POINTER(DfaInfo), VP, VP,

@@ -366,6 +366,10 @@ bool build_regex(rure *re) {
     return re->nfa_ok;
   }
   re->dfa_ok = true;
+  // the tile kernel's skip rule: proved on the packed table, or off
+  tile_skip_analyse(re->expr, re->pf.lds.data(), re->pf.all ? 0 : re->pf.hot, re->pf.ustart1, &re->tskip);
+  if (!re->tskip.ok && knob(Knob::Timing) == 1)
+    fprintf(stderr, "tile_skip: %s: not eligible: %s\n", re->pattern.c_str(), re->tskip.why.c_str());
   return true;
 }
 
@@ -654,7 +658,7 @@ DevTables *regex_device(rure *re, std::string *err) {
   NfaOffsets no{};
   if (re->nfa_ok) no = add_nfa(b, re->nt);
   size_t o_lds = 0, o_lds_s = 0, o_full = 0, o_eof = 0, o_start = 0, o_rfull = 0, o_reof = 0, o_rstart = 0,
-         o_rlds = 0;
+         o_rlds = 0, o_sa = 0;
   const PackedFwd &pf = re->pf;
   const DenseDfa &rv = re->drev;
   if (re->dfa_ok) {
@@ -670,6 +674,7 @@ DevTables *regex_device(rure *re, std::string *err) {
     o_reof = b.add(rv.eof_match.data(), rv.eof_match.size());
     o_rstart = b.add(rstart.data(), 256);
     o_rlds = b.add(re->pr.lds.data(), re->pr.lds.size());
+    if (re->tskip.ok) o_sa = b.add(re->tskip.sa, sizeof(re->tskip.sa));
   }
   const bool mt_lane = needs_mt_lane(re->xl);
   LitOffsets lp{}, ls{};
@@ -760,6 +765,7 @@ DevTables *regex_device(rure *re, std::string *err) {
     t.f.ustart1 = pf.ustart1;
     t.f.nonempty = can_match_empty(re->nfa) ? 0 : 1;
     set_prefix_skip(re, &t.f);
+    if (re->tskip.ok) tile_skip_dev(re->tskip, (const uint16_t *)(base + o_sa), &t.f.skip);
     // a regex anchored at the end and not at the start runs the reverse DFA
     // from the end of the text (exec.rs:1175-1177, 671-688)
     t.anchored_rev = !re->nfa.anchored_start && re->nfa.anchored_end;

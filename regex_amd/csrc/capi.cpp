@@ -1250,6 +1250,28 @@ int rure_amd_suffix_forward(rure *re) {
   if (!re) return RURE_AMD_ERR_ARG;
   return build_iter_dfa(re) && re->suffix_fwd ? 1 : 0;
 }
+int rure_amd_tile_skip_info(rure *re, rure_amd_tile_skip *info) {
+  if (!re || !info) return RURE_AMD_ERR_ARG;
+  memset(info, 0, sizeof(*info));
+  if (!build_regex(re) || !re->dfa_ok) return RURE_AMD_ERR_DFA;
+  const TileSkip &k = re->tskip;
+  info->eligible = k.ok ? 1 : 0;
+  info->used = k.ok && k.use ? 1 : 0;
+  info->m = (int32_t)k.m;
+  info->anchor_a = k.ok ? (int32_t)k.pa : -1;
+  info->anchor_b = k.ok ? (int32_t)k.pb : -1;
+  return RURE_AMD_OK;
+}
+
+int64_t rure_amd_tile_skip_simulate(rure *re, const uint8_t *hay, size_t len, uint32_t *states_skip,
+                                    uint32_t *states_exact, uint8_t *dirty) {
+  if (!re || (!hay && len) || !states_skip || !states_exact || !dirty) return RURE_AMD_ERR_ARG;
+  if (!build_regex(re) || !re->dfa_ok) return RURE_AMD_ERR_DFA;
+  if (!re->tskip.ok) return RURE_AMD_ERR_ARG;
+  return (int64_t)tile_skip_simulate(re->tskip, re->pf.lds.data(), re->pf.hot, re->pf.full.data(),
+                                     (uint32_t)re->dfwd.n_match_end, hay, len, states_skip, states_exact, dirty);
+}
+
 int rure_amd_debug_set(const char *spec) { return rure_amd::knob_set(spec) ? RURE_AMD_OK : RURE_AMD_ERR_ARG; }
 
 

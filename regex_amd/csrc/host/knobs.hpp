@@ -53,6 +53,7 @@ enum class Knob : int {
   SetChunk,        // the unit size in bytes of the chunked RegexSet scan (floor 16)
   LazyLong,        // 0: few long haystacks of a regex past the eager budgets keep the Pike VM; 2: chunked on the on-demand DFA at any length and count
   LazyChunk,       // the unit size in bytes of that chunked scan (floor 16, no odd-lines rounding)
+  TileSkip,        // 0: the tile kernel never skips a tile's walk (tile_skip_device.hpp)
   kCount
 };
 

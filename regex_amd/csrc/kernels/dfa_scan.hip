@@ -263,10 +263,31 @@ hipError_t launch_lit_find(int mode, const BatchDev &b, const FwdDfaDev &f, void
 static constexpr int kTileTab = 64 * kRow + 256;   // largest LDS fast table of the tile path (hot + 1 <= 64 rows)
 static constexpr int kTileTabSmall = 16 * kRow + 96; // hot + 1 <= 16 rows
 
-template <int MODE, int TAB, int STRIDE>
-__global__ __launch_bounds__(256) void dfa_fwd_tile_kernel(BatchDev bt, FwdDfaDev f, RevDfaDev r, void *out,
-                                                           uint64_t gscatter) {
+// SKIP (byte table only; a regex the host found eligible, host/tile_skip.cpp):
+// each tile is first streamed through the skip rule of tile_skip_device.hpp.
+// When no lane of the wave finds it dirty the walk is left out, and each
+// lane's state is chain16(s0, the tile's last 16 bytes); else the whole wave
+// walks the tile as without SKIP.  Either way every lane's state is exact at
+// every tile boundary.
+struct TileSkipSrc {  // a lane's row of the stage buffer
+  const uint4 *buf;
+  int lane, sw;
+  __device__ __forceinline__ uint4 row(int r) const { return buf[lane * 8 + (r ^ sw)]; }
+  __device__ __forceinline__ uint32_t byte(uint32_t p) const {
+    return ((const uint8_t *)buf)[(lane * 8 + ((p >> 4) ^ sw)) * 16 + (p & 15)];
+  }
+};
+
+template <int MODE, int TAB, int STRIDE, bool SKIP = false>
+__global__ __launch_bounds__(256, SKIP && TAB == kTileTabSmall ? 4 : 1) void dfa_fwd_tile_kernel(BatchDev bt,
+                                                                                                 FwdDfaDev f,
+                                                                                                 RevDfaDev r,
+                                                                                                 void *out,
+                                                                                                 uint64_t gscatter) {
+  static_assert(!SKIP || STRIDE == 1, "the skip rule reads the byte table");
   __shared__ __attribute__((aligned(16))) uint8_t tab[TAB];
+  __shared__ uint16_t sa[SKIP ? 128 : 1];
+  if (SKIP && threadIdx.x < 128) sa[threadIdx.x] = f.skip.sa[threadIdx.x];
   const uint8_t *img = STRIDE == 1 ? f.lds_image : f.lds_image_s;
   const uint32_t img_bytes = STRIDE == 1 ? f.lds_bytes : f.lds_bytes_s;
   __shared__ __attribute__((aligned(16))) uint4 stage[4][64 * 8];
@@ -298,6 +319,7 @@ __global__ __launch_bounds__(256) void dfa_fwd_tile_kernel(BatchDev bt, FwdDfaDe
     if (L_.s >= f.n_normal) L_.done = true;
     L_.fast = STRIDE > 1 && !L_.done && L_.s < f.hot_s;
     L_.t = L_.fast ? L_.s * f.P : 0;
+    TileSkipLane K_{};
     // this lane's share of each coalesced tile load: haystack g*64 + 8k + src_h,
     // 16-byte segment src_seg (rows past the batch end re-read row n-1; unused)
     uint64_t hh0 = g * 64 + src_h;
@@ -322,9 +344,32 @@ __global__ __launch_bounds__(256) void dfa_fwd_tile_kernel(BatchDev bt, FwdDfaDe
       RURE_STAGE(4, n4) RURE_STAGE(5, n5) RURE_STAGE(6, n6) RURE_STAGE(7, n7)
       wave_lds_sync();
       const uint64_t an = (at + 128 < L128) ? at + 128 : at;
-      RURE_LOAD_TILE(an)
+      if (!SKIP) { RURE_LOAD_TILE(an) }
       uint4 cur = buf[lane * 8 + sw];
-      if (STRIDE == 1) {
+      bool walk = true;
+      uint32_t pdirty = 0;
+      if (SKIP) {
+        pdirty = tile_skip_dirty(f.skip, sa, TileSkipSrc{buf, lane, sw}, K_, L_.s);
+        // The next tile's loads are issued after the scan here: with their 32
+        // registers live through it the kernel needs 162 VGPRs (3 waves per
+        // SIMD), this way 119 (4 waves).  The fence keeps the walk below from
+        // reusing the scan's rows in registers, for the same reason.
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        RURE_LOAD_TILE(an)
+        if (!__any(!L_.done && (pdirty & kSkipDirty))) {
+          const uint4 v = buf[lane * 8 + (7 ^ sw)];
+          uint32_t t = f.skip.s0;
+          t = fast4(t, v.x, tab);
+          t = fast4(t, v.y, tab);
+          t = fast4(t, v.z, tab);
+          t = fast4(t, v.w, tab);
+          if (!L_.done) L_.s = t;
+          K_.prev_dirty = 0;
+          walk = false;
+        }
+      }
+      if (!walk) {
+      } else if (STRIDE == 1) {
         // Branch-free pass over the tile's 128 bytes through the LDS table:
         // the sentinel row (`hot`) is absorbing, so a lane that leaves the
         // hot states (or is done, or starts outside them) just rides the
@@ -361,6 +406,7 @@ __global__ __launch_bounds__(256) void dfa_fwd_tile_kernel(BatchDev bt, FwdDfaDe
         } else if (!L_.done) {
           L_.s = t;
         }
+        if (SKIP) K_.prev_dirty = (pdirty & kSkipOwn) || bad < 8;
       } else {
 #pragma unroll 1
         for (int m = 0; m < 8; ++m) {
@@ -1070,6 +1116,16 @@ static hipError_t launch_tile_s(const BatchDev &b, const FwdDfaDev &f, const Rev
   auto gcd = [](uint64_t a, uint64_t c) { while (c) { uint64_t t = a % c; a = c; c = t; } return a; };
   while (ngroups > 1 && gcd(mul, ngroups) != 1) mul += 2;
   if (ngroups <= 1) mul = 0;
+  // the skip rule: an eligible regex on the byte table (tileskip=0: never)
+  if (STRIDE == 1 && f.skip.on && knob(Knob::TileSkip) != 0) {
+    if (bytes <= (uint32_t)kTileTabSmall)
+      hipLaunchKernelGGL((dfa_fwd_tile_kernel<MODE, kTileTabSmall, 1, true>), dim3(grid), dim3(256), 0, st, b, f, r,
+                         out, mul);
+    else
+      hipLaunchKernelGGL((dfa_fwd_tile_kernel<MODE, kTileTab, 1, true>), dim3(grid), dim3(256), 0, st, b, f, r, out,
+                         mul);
+    return hipGetLastError();
+  }
   if (bytes <= (uint32_t)kTileTabSmall)
     hipLaunchKernelGGL((dfa_fwd_tile_kernel<MODE, kTileTabSmall, STRIDE>), dim3(grid), dim3(256), 0, st, b, f, r, out,
                        mul);

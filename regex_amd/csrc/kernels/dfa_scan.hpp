@@ -6,6 +6,7 @@
 #include "../../../include/rure_amd.h"
 #include "../host/chunk_plan.hpp"
 #include "../host/knobs.hpp"
+#include "tile_skip_device.hpp"
 
 namespace rure_amd {
 
@@ -165,6 +166,9 @@ struct FwdDfaDev {
   const uint8_t *run_cls;
   const uint32_t *run_cp;
   uint32_t run_quit;  // some byte quits (bit 1): the run engine's flag is read back
+  // forward DFA of find / is_match / shortest_match only: the tile kernel's
+  // skip rule (tile_skip_device.hpp; skip.on = 0: the regex is not eligible)
+  TileSkipDev skip;
 };
 constexpr uint32_t kLexMaxRows = 24;  // lexer table rows (iter_spec_lex_tile_kernel's static LDS)
 constexpr uint32_t kLexUnit = kRow / 4;  // lexer entry -> row address multiplier

@@ -35,6 +35,7 @@
 #include "host/literal_sets.hpp"
 #include "host/program.hpp"
 #include "host/syntax.hpp"
+#include "host/tile_skip.hpp"
 #include "host/unicode_tables.h"
 #include "kernels/dfa_scan.hpp"
 
@@ -230,6 +231,7 @@ struct rure {
   std::string dfa_err;
   DenseDfa dfwd, drev;
   PackedFwd pf, pr;   // forward / reverse hot tables
+  TileSkip tskip;     // the tile kernel's skip rule for pf (host/tile_skip.hpp)
   // automata past the u16 tables (column form, u32; big_dfa.hip): batched
   // find / is_match / shortest_match only, when dfa_ok is false
   bool big_ok = false, big_built = false;
