@@ -193,9 +193,17 @@ int rure_amd_shortest_match_batch(rure *re, const rure_amd_batch *batch, size_t 
  * budget (no DFA; no Unicode word boundary) answers batches that fill the
  * device from its on-demand DFA: rows are built on the host as the text
  * needs them, so such a call synchronises `stream` between rounds, and the
- * first call on new text pays the construction (smaller batches, and a spent
- * memory budget, keep the Pike VM).  Each 64-pattern group of a larger set
- * takes these decisions for itself. */
+ * first call on new text pays the construction.  Few long fixed-stride
+ * haystacks of such a set (the thresholds above; not every pattern anchored
+ * at the start) are cut into the same units, which run on that automaton and
+ * step into a state's twin without the unanchored prefix at their cut: the
+ * call is synchronous likewise, reports RURE_AMD_PATH_LAZY_DFA, and
+ * rure_amd_last_set_units gives its units (rure_set_matches and
+ * rure_set_is_match on a long host buffer take it too).  Past the automaton's
+ * memory budget, or after 256 rounds, the Pike VM answers the whole batch; it
+ * also keeps the other batches of such a set (offset batches, sets anchored
+ * at the start, a Unicode word boundary).  Each 64-pattern group of a larger
+ * set takes these decisions for itself. */
 int rure_amd_set_matches_batch(rure_set *re, const rure_amd_batch *batch, uint64_t *mask,
                                void *stream);
 /* The same for any number of patterns: `words` >= ceil(rure_set_len / 64)
@@ -485,6 +493,21 @@ int rure_amd_set_lazy_export(rure_set *re, rure_amd_lazy_info *info, uint32_t *t
  * in discovery order: what one round of a batched call does between two
  * launches.  Returns 1, 0 when the memory budget is spent, or an error. */
 int rure_amd_set_lazy_build(rure_set *re, const uint32_t *states, size_t n, size_t ahead);
+/* The strip links of that automaton and what its states can still report
+ * (host only, for tests), one entry per state (`states` of
+ * rure_amd_set_lazy_export's info): strip as rure_amd_lazy_strip_export
+ * below (a twin may have no thread left and only the patterns its entry
+ * reported: a live id whose row is all dead); reach = u64, a superset of the
+ * patterns a walk from the state reports (those the program reaches from the
+ * state's threads whatever the bytes, plus those its entry reports; 0 for
+ * the dead state).  The chunked scan of few long haystacks steps into the
+ * twin at a unit's cut and leaves the unit once everything in reach is in the
+ * haystack's mask.  NULL arrays are skipped.  RURE_AMD_ERR_DFA where the set
+ * has no on-demand automaton or every pattern is anchored at the start. */
+int rure_amd_set_lazy_strip_export(rure_set *re, uint32_t *strip, uint64_t *reach);
+/* Makes the links of the n named states.  Returns 1, 0 when the memory
+ * budget is spent, or an error. */
+int rure_amd_set_lazy_strip_build(rure_set *re, const uint32_t *states, size_t n);
 /* The same for a regex (host only, for tests): the on-demand forward DFA that
  * answers find, is_match, shortest_match and find_iter over batches of a
  * regex whose forward DFA does not materialise.  info as above, rounds and
@@ -702,9 +725,10 @@ uint64_t rure_amd_last_iter_units(uint64_t *haystacks);
  * the batched call enqueued on its stream. */
 uint64_t rure_amd_last_long_units(uint64_t *haystacks, uint64_t *chunk);
 /* Diagnostics (host only, one value for the whole process likewise): the
- * units the last chunked RegexSet launch cut its batch into; *haystacks (may
- * be NULL) = that batch's haystack count, *chunk (may be NULL) = the unit size
- * in bytes.  All 0 before the first such launch and after a set call (a
+ * units the last chunked RegexSet call cut its batch into, on the set's DFA
+ * or on its on-demand DFA (also where that one gave up and the Pike VM
+ * answered); *haystacks (may be NULL) = that batch's haystack count, *chunk
+ * (may be NULL) = the unit size in bytes.  All 0 before the first such launch and after a set call (a
  * 64-pattern group's, for larger sets) that did not chunk.  The host knows
  * the geometry: this call waits for nothing. */
 uint64_t rure_amd_last_set_units(uint64_t *haystacks, uint64_t *chunk);

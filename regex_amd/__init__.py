@@ -1235,10 +1235,46 @@ class RegexSet(object):
             _check(rc, "set_lazy_build")
         return rc == 1
 
+    def _lazy_strip_export(self, want_reach):
+        import numpy as np
+        _check(N.rure_amd_set_lazy_strip_export(self._set, None, None), "set_lazy_strip_export")
+        info = N.LazyInfo()
+        _check(N.rure_amd_set_lazy_export(self._set, ctypes.byref(info), None, None, None, None, None, None),
+               "set_lazy_export")
+        out = np.zeros(info.states, dtype=np.uint64 if want_reach else np.uint32)
+        _check(N.rure_amd_set_lazy_strip_export(self._set, None if want_reach else out.ctypes.data,
+                                                out.ctypes.data if want_reach else None), "set_lazy_strip_export")
+        return out
+
+    def lazy_strip(self):
+        """The strip links of the set's on-demand DFA as they stand (see
+        Regex.lazy_strip).  A twin may be a state without threads that only
+        carries the patterns its entry reported: its row is all dead.  Raises
+        RuntimeError where the set has no such automaton or every pattern is
+        anchored at the start."""
+        return self._lazy_strip_export(False)
+
+    def lazy_reach(self):
+        """One uint64 per state of the on-demand DFA: a superset of the
+        patterns a walk from the state reports (0 for the dead state); a unit
+        of the chunked scan past its cut leaves once its haystack's mask holds
+        them all.  Raises as lazy_strip."""
+        return self._lazy_strip_export(True)
+
+    def lazy_strip_build(self, states):
+        """Makes the strip links of `states` (a new twin is a new state with
+        its row not built); False once the memory budget is spent."""
+        arr = (ctypes.c_uint32 * max(len(states), 1))(*[int(s) for s in states])
+        rc = N.rure_amd_set_lazy_strip_build(self._set, arr, len(states))
+        if rc < 0:
+            _check(rc, "set_lazy_strip_build")
+        return rc == 1
+
     @staticmethod
     def last_long_units():
         """(units, haystacks, chunk) of the last chunked RegexSet launch of
-        this process; (0, 0, 0) after a set call that did not chunk."""
+        this process (set_long_kernel, or the on-demand DFA's chunked scan);
+        (0, 0, 0) after a set call that did not chunk."""
         n, c = ctypes.c_uint64(0), ctypes.c_uint64(0)
         units = N.rure_amd_last_set_units(ctypes.byref(n), ctypes.byref(c))
         return int(units), int(n.value), int(c.value)

@@ -247,6 +247,8 @@ rure_amd_set_lazy_build = _sig("rure_amd_set_lazy_build", ctypes.c_int, VP, VP, 
 rure_amd_lazy_export = _sig("rure_amd_lazy_export", ctypes.c_int, VP, ctypes.POINTER(LazyInfo), VP, VP, VP, VP, VP)
 rure_amd_lazy_build = _sig("rure_amd_lazy_build", ctypes.c_int, VP, VP, c_size, c_size)
 rure_amd_lazy_strip_export = _sig("rure_amd_lazy_strip_export", ctypes.c_int, VP, VP)
+rure_amd_set_lazy_strip_export = _sig("rure_amd_set_lazy_strip_export", ctypes.c_int, VP, VP, VP)
+rure_amd_set_lazy_strip_build = _sig("rure_amd_set_lazy_strip_build", ctypes.c_int, VP, VP, c_size)
 rure_amd_lazy_strip_build = _sig("rure_amd_lazy_strip_build", ctypes.c_int, VP, VP, c_size)
 rure_amd_last_lazy_long = _sig("rure_amd_last_lazy_long", ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
                                ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32),

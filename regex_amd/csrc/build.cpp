@@ -1048,9 +1048,10 @@ bool build_set_long(rure_set *rs) {
 // mask word; each 64-pattern group of a larger set is such a set itself).
 // Sets get no eager u32 tier: past the u16 budget the states a batch visits
 // are built on demand within kBigDfaBytes (knob big_bytes).
-LazyDfa *set_lazy(rure_set *rs) {
+LazyDfa *set_lazy(rure_set *rs, bool locked) {
   if (!rs || rs->single || rs->exprs.size() < 2 || rs->exprs.size() > 64 || !rs->groups.empty()) return nullptr;
-  std::lock_guard<std::mutex> g(rs->mu);
+  std::unique_lock<std::mutex> g(rs->mu, std::defer_lock);
+  if (!locked) g.lock();
   if (rs->lazy_tried) return rs->lazy.get();
   rs->lazy_tried = true;
   if (rs->fwd.has_unicode_word_boundary) return nullptr;

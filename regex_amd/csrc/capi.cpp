@@ -1017,6 +1017,28 @@ int rure_amd_set_lazy_build(rure_set *rs, const uint32_t *states, size_t n, size
   return L->expand(ahead) ? 1 : 0;
 }
 
+int rure_amd_set_lazy_strip_export(rure_set *rs, uint32_t *strip, uint64_t *reach) {
+  if (!rs || rs->single || rs->exprs.size() < 2) return RURE_AMD_ERR_ARG;
+  LazyDfa *L = set_lazy(rs);
+  if (!L || !L->has_strip()) return RURE_AMD_ERR_DFA;
+  std::lock_guard<std::mutex> g(rs->mu);
+  if (strip) memcpy(strip, L->strip.data(), L->strip.size() * 4);
+  if (reach) memcpy(reach, L->reach.data(), L->reach.size() * 8);
+  return RURE_AMD_OK;
+}
+
+int rure_amd_set_lazy_strip_build(rure_set *rs, const uint32_t *states, size_t n) {
+  if (!rs || rs->single || rs->exprs.size() < 2 || (!states && n)) return RURE_AMD_ERR_ARG;
+  LazyDfa *L = set_lazy(rs);
+  if (!L || !L->has_strip()) return RURE_AMD_ERR_DFA;
+  std::lock_guard<std::mutex> g(rs->mu);
+  for (size_t i = 0; i < n; ++i) {
+    if (states[i] >= L->nstates()) return RURE_AMD_ERR_ARG;
+    if (!L->strip_of(states[i])) return 0;
+  }
+  return 1;
+}
+
 int rure_amd_lazy_export(rure *re, rure_amd_lazy_info *info, uint32_t *trans, uint8_t *eof, uint8_t *built,
                          uint32_t *start, uint8_t *colmap) {
   if (!re) return RURE_AMD_ERR_ARG;

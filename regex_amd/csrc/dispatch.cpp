@@ -314,8 +314,9 @@ static bool big_batch(const BatchDev &b, const DevTables &t) {
   return b.count >= (uint64_t)t.cus * 64;
 }
 
-// The rounds of a batched scan on an on-demand DFA (a regex's: run_lazy and
-// run_lazy_iter; a set's: run_lazy_set): `launch` runs one round of the
+// The rounds of a batched scan on an on-demand DFA (a regex's: run_lazy,
+// run_lazy_long and run_lazy_iter; a set's: run_lazy_set and
+// run_lazy_set_long): `launch` runs one round of the
 // kernel; between rounds the host builds the rows the parked lanes need (and, ahead of them,
 // more rows in discovery order) and uploads the grown table, which stays in
 // t.lazy_buf for the next call.  Synchronous, as the reference's
@@ -353,11 +354,12 @@ static hipError_t lazy_rounds(LazyDfa &L, DevTables &t, uint64_t count, hipStrea
   uint64_t nin = 0;
   std::vector<Park> host;
   for (int round = 0; ok && e == hipSuccess; ++round) {
-    // the table: [colmap 256][start 512][now cap * 8][eof_mask cap * 8][eof cap][trans cap * ncol * 4][strip cap * 4]
-    // (now and eof_mask: a set's, 8-byte aligned; none for a regex.  strip:
-    // once a chunked call has made a link)
+    // the table: [colmap 256][start 512][now cap * 8][eof_mask cap * 8][reach cap * 8][eof cap]
+    // [trans cap * ncol * 4][strip cap * 4]
+    // (now, eof_mask and reach: a set's, 8-byte aligned; none for a regex.
+    // strip: once a chunked call has made a link)
     const size_t ns = L.nstates(), nm = L.is_set ? ns : 0, nl = L.nlinks() ? ns : 0;
-    const size_t need = 768 + nm * 16 + ns + ns * (size_t)L.ncol * 4 + nl * 4 + 16;
+    const size_t need = 768 + nm * 24 + ns + ns * (size_t)L.ncol * 4 + nl * 4 + 16;
     if (need > t.lazy_cap) {
       if ((e = hipStreamSynchronize(st)) != hipSuccess) break;
       if (t.lazy_buf) (void)hipFree(t.lazy_buf);
@@ -367,10 +369,12 @@ static hipError_t lazy_rounds(LazyDfa &L, DevTables &t, uint64_t count, hipStrea
       if ((e = hipMalloc(&t.lazy_buf, t.lazy_cap)) != hipSuccess) { t.lazy_cap = 0; break; }
     }
     uint8_t *base = (uint8_t *)t.lazy_buf;
-    const size_t o_now = 768, o_mask = o_now + nm * 8, o_eof = o_mask + nm * 8, o_trans = (o_eof + ns + 15) & ~(size_t)15;
+    const size_t o_now = 768, o_mask = o_now + nm * 8, o_reach = o_mask + nm * 8, o_eof = o_reach + nm * 8;
+    const size_t o_trans = (o_eof + ns + 15) & ~(size_t)15;
     const size_t o_strip = o_trans + ns * (size_t)L.ncol * 4;
     // Uploaded unless the device copy is this very table: states, rows and
-    // links only ever grow, so their counts name its contents.  A call over text
+    // links only ever grow, so their counts name its contents (a state's masks,
+    // reach among them, are set when it is interned).  A call over text
     // whose rows exist copies nothing (1.4 M states are 186 MB).
     if (t.lazy_up_states != ns || t.lazy_up_built != L.nbuilt() || t.lazy_up_links != L.nlinks()) {
       t.lazy_up_states = 0;
@@ -379,7 +383,8 @@ static hipError_t lazy_rounds(LazyDfa &L, DevTables &t, uint64_t count, hipStrea
       };
       if ((e = up(0, L.colmap, 256)) != hipSuccess || (e = up(256, L.start, 512)) != hipSuccess ||
           (e = up(o_now, L.now.data(), nm * 8)) != hipSuccess ||
-          (e = up(o_mask, L.eof_mask.data(), nm * 8)) != hipSuccess || (e = up(o_eof, L.eof.data(), ns)) != hipSuccess ||
+          (e = up(o_mask, L.eof_mask.data(), nm * 8)) != hipSuccess ||
+          (e = up(o_reach, L.reach.data(), nm * 8)) != hipSuccess || (e = up(o_eof, L.eof.data(), ns)) != hipSuccess ||
           (e = up(o_trans, L.trans.data(), L.trans.size() * 4)) != hipSuccess ||
           (e = up(o_strip, L.strip.data(), nl * 4)) != hipSuccess)
         break;
@@ -392,6 +397,7 @@ static hipError_t lazy_rounds(LazyDfa &L, DevTables &t, uint64_t count, hipStrea
     f.start = (const uint32_t *)(base + 256);
     f.now = nm ? (const uint64_t *)(base + o_now) : nullptr;
     f.eof_mask = nm ? (const uint64_t *)(base + o_mask) : nullptr;
+    f.reach = nm ? (const uint64_t *)(base + o_reach) : nullptr;
     f.eof = base + o_eof;
     f.trans = (const uint32_t *)(base + o_trans);
     f.strip = nl ? (const uint32_t *)(base + o_strip) : nullptr;
@@ -690,8 +696,8 @@ static hipError_t run_lazy_set(rure_set *rs, const BatchDev &b, const DevTables 
 // The on-demand DFA for a set past the eager budget, on batches that fill
 // the device: the regex rule (lazy_batch).  Knob lazy: 0 never, 1 any set
 // that can have it, also one with an eager DFA (tests); big: 2 any batch, 0
-// keeps the Pike VM.  rs is null for the single-haystack host calls, which
-// keep the Pike VM.
+// keeps the Pike VM.  Not asked for the single-haystack host calls (run_set:
+// locked), which keep the Pike VM below the chunked scan's span.
 static bool lazy_set_batch(rure_set *rs, const BatchDev &b, const DevTables &t) {
   if (!rs || !rs->nfa_ok || knob(Knob::Lazy) == 0) return false;
   const bool force = knob(Knob::Lazy) == 1;
@@ -699,11 +705,65 @@ static bool lazy_set_batch(rure_set *rs, const BatchDev &b, const DevTables &t) 
   return set_lazy(rs) != nullptr;
 }
 
+// Few long fixed-stride haystacks of a set without an eager DFA: the units of
+// set_long_batch (its span and count thresholds, its chunk rule) on the
+// set's on-demand DFA (run_lazy_set_long), as lazy_long_batch sends a regex's.
+// Asked after set_long_batch: a set with an eager DFA keeps set_long_kernel.
+// Not for batches that fill the device (big_batch: lazy_set_kernel, one lane
+// per haystack), offset batches, sets set_lazy refuses, nor a program
+// anchored at the start (no `.*?` prefix, so no links).  Knobs: the regex
+// path's lazy_long (0 never, 2 at any length and count) and lazy_chunk (the
+// unit size in bytes); lazy = 0 and set_long = 0 turn the path off, lazy = 1
+// takes a set with an eager DFA too.  set_long = 2 and set_chunk do not force
+// it.  locked: the caller holds rs->mu (the single-haystack calls).
+static bool lazy_set_long_batch(rure_set *rs, const BatchDev &b, const DevTables &t, bool locked, uint64_t *chunk) {
+  const long long mode = knob(Knob::LazyLong);
+  if (!rs || !rs->nfa_ok || mode == 0 || knob(Knob::Lazy) == 0 || knob(Knob::SetLong) == 0) return false;
+  if (b.offs || b.count == 0) return false;
+  if (t.has_dfa && knob(Knob::Lazy) != 1) return false;
+  const uint64_t span = b.length > b.start ? b.length - b.start : 0;
+  if (mode != 2 && (big_batch(b, t) || span < kLongSpan || b.count >= (uint64_t)t.cus * 128)) return false;
+  if (rs->fwd.dotstar_end == 0) return false;  // anchored at the start (before any automaton is made for it)
+  LazyDfa *L = set_lazy(rs, locked);
+  if (!L || !L->has_strip()) return false;
+  *chunk = unit_bytes(span, b.count, lanes_in_flight(t.cus, Knob::LongLanes), kLongFloor);
+  if (knob(Knob::LazyChunk) > 0) *chunk = std::max<uint64_t>(16, knob(Knob::LazyChunk));
+  return true;
+}
+
+// Rounds of lazy_set_long_kernel over the units until none is parked: the
+// haystacks' words are zeroed once, before the first round, and the units OR
+// into them.  Synchronous, as run_lazy_set; a spent budget or kLazyRounds
+// rounds send the whole batch to the Pike VM (which writes every word).
+static hipError_t run_lazy_set_long(rure_set *rs, const BatchDev &b, const DevTables &tc, uint64_t chunk,
+                                    uint64_t *out, hipStream_t st, bool locked) {
+  DevTables &t = const_cast<DevTables &>(tc);  // the set's own entry of rure_set::dev
+  std::unique_lock<std::mutex> g(rs->mu, std::defer_lock);
+  if (!locked) g.lock();
+  const size_t np = rs->exprs.size();
+  const uint64_t all = np >= 64 ? ~0ull : (1ull << np) - 1;
+  const uint64_t units = lazy_long_units(b, chunk);
+  hipError_t e = hipMemsetAsync(out, 0, b.count * 8, st);
+  if (e != hipSuccess) return e;
+  bool ok = true;
+  e = lazy_rounds<LazyLongPark>(*rs->lazy, t, units, st, &ok, &rs->lazy_rounds,
+                                [&](const LazyDfaDev &f, const LazyLongPark *in, uint64_t nin, LazyLongPark *po,
+                                    unsigned long long *cnt) {
+                                  return launch_lazy_set_long(b, f, all, chunk, in, nin, po, cnt, out, st, t.cus);
+                                });
+  rs->lazy_fell_back = e == hipSuccess && !ok;
+  note_set_units(units, b.count, chunk);
+  if (e != hipSuccess || ok) return e;
+  return run_pike(MODE_SET, false, b, t, out, st);  // the whole batch again
+}
+
 // exec.rs:998-1038 many_matches_at for a batch.  sl: the chunked scan's
 // automaton where set_long_batch chose it (chunk its unit), else null.  rs:
-// the set, for a batched call (the on-demand DFA is its host object).
+// the set (the on-demand DFA is its host object); locked: the caller holds
+// rs->mu (the single-haystack host calls, which take the chunked on-demand
+// scan and otherwise keep the Pike VM).
 static hipError_t run_set(rure_set *rs, const BatchDev &b, const DevTables &t, uint64_t *out, hipStream_t st,
-                          int dfa_grid, const SetLongDev *sl, uint64_t chunk) {
+                          int dfa_grid, const SetLongDev *sl, uint64_t chunk, bool locked = false) {
   if (sl) {
     uint64_t units = 0;
     const hipError_t e = launch_set_long(b, *sl, chunk, out, st, t.cus, &units);
@@ -713,8 +773,10 @@ static hipError_t run_set(rure_set *rs, const BatchDev &b, const DevTables &t, u
     }
     return e;
   }
+  uint64_t lchunk = 0;
+  if (lazy_set_long_batch(rs, b, t, locked, &lchunk)) return run_lazy_set_long(rs, b, t, lchunk, out, st, locked);
   note_set_units(0, 0, 0);
-  if (lazy_set_batch(rs, b, t)) return run_lazy_set(rs, b, t, out, st);
+  if (!locked && lazy_set_batch(rs, b, t)) return run_lazy_set(rs, b, t, out, st);
   if (!t.has_dfa) return run_pike(MODE_SET, false, b, t, out, st);
   const auto step = [&](const BatchDev &bq) {
     return t.use_cores ? launch_set_cores(bq, t.c, out, st, t.cus) : launch_dfa_set(bq, t.s, out, st, dfa_grid);
@@ -848,7 +910,7 @@ uint64_t set_single_call(rure_set *rs, const uint8_t *hay, size_t len, size_t st
   hipStream_t st = rs->stage.stream;
   if (len && !hip_ok(hipMemcpyAsync(rs->stage.hay, hay, len, hipMemcpyHostToDevice, st), &err)) die(err);
   BatchDev b{rs->stage.hay, nullptr, 0, len, 1, start};
-  if (!hip_ok(run_set(nullptr, b, *t, rs->stage.res, st, 1, sl, chunk), &err)) die(err);
+  if (!hip_ok(run_set(rs, b, *t, rs->stage.res, st, 1, sl, chunk, true), &err)) die(err);
   uint64_t out = 0;
   if (!hip_ok(hipMemcpyAsync(&out, rs->stage.res, 8, hipMemcpyDeviceToHost, st), &err)) die(err);
   if (!hip_ok(hipStreamSynchronize(st), &err)) die(err);

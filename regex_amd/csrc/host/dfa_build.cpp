@@ -84,6 +84,36 @@ class Builder {
     if (s >= 2) step_eof(keys_[s], &m);
     return m;
   }
+  // Sets: every Match slot raw state s can still report (LazyDfa::reach): the
+  // slots the program graph reaches from the threads of its key, whatever the
+  // bytes and look-around conditions on the way, plus those its entry reports.
+  uint64_t lazy_reach(uint32_t s) {
+    if (s < 2) return 0;
+    if (inst_reach_.empty()) {
+      const size_t n = p_.insts.size();
+      inst_reach_.assign(n, 0);
+      for (bool changed = true; changed;) {
+        changed = false;
+        for (size_t ip = n; ip-- > 0;) {
+          const Inst &in = p_.insts[ip];
+          uint64_t m = inst_reach_[ip];
+          if (in.op == OP_MATCH) m |= in.x < 64 ? 1ull << in.x : 0;
+          else if (in.x < n) m |= inst_reach_[in.x];
+          if (in.op == OP_SPLIT && in.y < n) m |= inst_reach_[in.y];
+          if (m != inst_reach_[ip]) { inst_reach_[ip] = m; changed = true; }
+        }
+      }
+    }
+    const std::string &key = keys_[s];
+    uint64_t m = now_of(key);
+    for (size_t k = 1; k + 4 <= key.size(); k += 4) {
+      uint32_t ip;
+      memcpy(&ip, key.data() + k, 4);
+      if (ip == 0xFFFFFFFFu) break;
+      m |= inst_reach_[ip];
+    }
+    return m;
+  }
   uint32_t lazy_start(int fi) const { return start_used_[fi] ? start_raw_[fi] : 0; }
   // The twin of raw state s without the `.*?` prefix threads (strip_key),
   // interned after every state there is when it is new; 0 = dead.  A program
@@ -209,6 +239,7 @@ class Builder {
   bool start_used_[128];
   int lazy_ncls_ = 0;
   uint8_t lazy_rep_[256] = {0};
+  std::vector<uint64_t> inst_reach_;  // lazy_reach: per instruction, the Match slots its successors reach
 
   // dfa.rs:1073-1134
   void follow(uint32_t ip0, SparseSet &q, const EmptyFlags &f) {
@@ -735,7 +766,11 @@ uint32_t LazyDfa::entry_of(uint32_t s) const {
 }
 
 // rows (unknown), EOF flags and (sets) masks for the states interned since
-// the last call
+// the last call.  reach[s] is a superset of what a walk from s reports (the
+// automaton is never finished, so it comes from the program graph, not from
+// the states): a chunked scan only leaves a unit on it, so a superset delays
+// that exit and never changes a mask.  A twin's threads are a subset of its
+// state's, and so is its reach.
 void LazyDfa::sync_new() {
   const uint32_t n = impl_->b.lazy_states();
   for (uint32_t s = (uint32_t)eof.size(); s < n; ++s) {
@@ -743,6 +778,7 @@ void LazyDfa::sync_new() {
     if (is_set) {
       now.push_back(impl_->b.lazy_now(s));
       eof_mask.push_back(impl_->b.lazy_eof_mask(s));
+      reach.push_back(impl_->b.lazy_reach(s));
     }
     built.push_back(s < 2 ? 1 : 0);
     strip.push_back(s < 2 ? s : kLazyUnknown);

@@ -88,7 +88,8 @@ bool build_dense_dfa(const Program &prog, const DfaBuildLimits &lim, DenseDfa *o
 // Unicode word boundaries keep the Pike VM).  For a set program the match
 // bit marks the states whose entry reports matches (now != 0, the states
 // Builder numbers [n_normal, n_match_end)), now / eof_mask are
-// DenseDfa::now_mask / eof_mask of the raw states, and eof is unused.
+// DenseDfa::now_mask / eof_mask of the raw states, reach bounds what a walk
+// from the state can report (the chunked scan's early exit), and eof is unused.
 constexpr uint32_t kLazyMatch = 0x80000000u, kLazyUnknown = 0x7FFFFFFFu;
 class LazyDfa {
  public:
@@ -121,6 +122,7 @@ class LazyDfa {
   bool is_set = false;            // a set program: now / eof_mask per state (else empty)
   std::vector<uint64_t> now;      // Match slots reported by the step into the state
   std::vector<uint64_t> eof_mask; // Match slots the EOF step from the state reaches
+  std::vector<uint64_t> reach;    // Match slots a walk from the state can still report, or more (0 for dead)
  private:
   struct Impl;
   Impl *impl_ = nullptr;

@@ -10,8 +10,8 @@
 // eagerly (dfa_build.cpp, column form) so a lane only reads tables.  Past
 // that budget too, rows are built on demand between rounds of
 // lazy_dfa_kernel (a regex), lazy_long_kernel (its few long haystacks, cut
-// into units), lazy_iter_kernel (its find_iter) or lazy_set_kernel (a
-// RegexSet's matches).
+// into units), lazy_iter_kernel (its find_iter), lazy_set_kernel (a
+// RegexSet's matches) or lazy_set_long_kernel (its few long haystacks).
 //
 // Execution: one lane per haystack (lazy_long_kernel: per unit).  A 16-byte chunk's columns come from the
 // LDS column map first (independent of the state), then the dependent chain
@@ -647,6 +647,129 @@ __global__ __launch_bounds__(1024) void lazy_long_kernel(BatchDev bt, Geo g, uin
   }
 }
 
+// RegexSet matches over few long fixed-stride haystacks on a set's on-demand
+// DFA: the units, the strip at c1 - 1 and the OR into the haystack's word of
+// set_long_kernel (set_long.hip), with the walk, staging and phases of
+// lazy_long_kernel and the set bookkeeping of lazy_set_kernel (now[] read on
+// entries with the match bit, eof_mask[] where a unit reaches the end of the
+// text alive; the mask travels in LazyLongPark::last).  out[h] is zeroed by
+// the caller before the first round and only ever ORed into.
+//
+// A unit publishes where it finishes, inside the walk (lazy_long_kernel's
+// note), and once per 512 bytes of text it ORs in the bits the word lacks and
+// reads the word back: it leaves when every pattern of the set is there, or,
+// past its cut, when everything its state can still report is (reach[s], a
+// superset: a lingering `.*` thread need not drag the unit to the end of the
+// haystack).  512 bytes as lazy_long_kernel, not set_long_kernel's 4096: a
+// byte here is a dependent table read, not a quarter of a packed LDS lookup,
+// so the poll (two loads and at most one atomic, none in the per-byte chain)
+// is as small a share of the walk, and the other lanes of the wave wait for a
+// unit that could have left at most that long.  The twin a unit steps into
+// may be a state without threads (its row is all dead): any id but 0 walks on.
+__global__ __launch_bounds__(1024) void lazy_set_long_kernel(BatchDev bt, Geo g, uint64_t nunits, LazyDfaDev f,
+                                                             uint64_t all, const LazyLongPark *in, uint64_t nin,
+                                                             LazyLongPark *park, unsigned long long *npark,
+                                                             unsigned long long *out) {
+  __shared__ __attribute__((aligned(16))) uint32_t hot_rows[kBigLdsBytes / 4];
+  __shared__ uint8_t colmap[256];
+  const uint32_t nhot = f.hot * f.ncol;
+  for (uint32_t i = threadIdx.x; i < nhot; i += blockDim.x) hot_rows[i] = f.trans[i];
+  for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x) colmap[i] = f.colmap[i];
+  __syncthreads();
+  const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x, nl = in ? nin : nunits;
+  for (uint64_t l = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; l < nl; l += nthreads) {
+    const uint64_t u = in ? in[l].u : l;
+    uint64_t h, len, c0, c1;
+    const uint8_t *base;
+    unit_bounds<false>(bt, g, u, &h, &base, &len, &c0, &c1);
+    const bool cut = c1 > c0 && c1 - 1 <= len;  // as set_long_kernel
+    uint64_t mask = 0, p = c0;
+    uint32_t s = 0, phase = cut ? kLazyLongBefore : kLazyLongAfter;
+    bool done = c0 > len, parked = false;  // done: no EOF step (a search from past the end reports nothing)
+    uintptr_t nblk = 0;  // the block `nxt` holds (0: none)
+    uint4 nxt = make_uint4(0, 0, 0, 0);
+    if (in) {
+      p = in[l].p;
+      mask = in[l].last;
+      s = in[l].s;
+      phase = in[l].phase;
+    } else if (!done) {
+      s = f.start[fwd_flag_index(base, len, c0)] & ~kLazyMatchBit;
+      done = s == 0;  // dead start state (dfa.rs:484)
+    }
+    while (!done) {
+      if (phase == kLazyLongAtCut) {
+        const uint32_t e = f.strip ? f.strip[s] : kLazyUnknownEntry;
+        if (e == kLazyUnknownEntry) {
+          parked = true;
+          break;
+        }
+        if (e == 0) {
+          done = true;  // no thread started in the unit is alive
+          if (mask) atomicOr(&out[h], (unsigned long long)mask);
+          break;
+        }
+        s = e;
+        phase = kLazyLongAfter;
+      }
+      const uint64_t lim = phase == kLazyLongBefore ? c1 - 1 : len;
+      while (!done && !parked && p < lim) {
+        const uintptr_t a = (uintptr_t)(base + p), blk = a & ~(uintptr_t)15;
+        if ((a & 0x1F0) == 0) {  // the haystack's word: add what it lacks, leave when nothing new can come
+          uint64_t seen = __hip_atomic_load(&out[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          const uint64_t lack = mask & ~seen;
+          if (lack) seen = atomicOr(&out[h], (unsigned long long)lack) | lack;
+          if ((all & ~seen) == 0 || (phase == kLazyLongAfter && (f.reach[s] & ~seen) == 0)) {
+            done = true;  // (what the unit had is in the word)
+            break;
+          }
+        }
+        const uint4 v = blk == nblk ? nxt : *(const uint4 *)blk;
+        if (blk + 16 < (uintptr_t)(base + len)) {
+          nblk = blk + 16;
+          nxt = *(const uint4 *)nblk;
+        }
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+        const uint32_t j0 = (uint32_t)(a & 15);
+        const uint32_t n = (uint32_t)min<uint64_t>(16 - j0, lim - p);
+        uint32_t j = j0;
+        for (; j < j0 + n; ++j) {
+          const uint32_t c = colmap[(w[j >> 2] >> (8 * (j & 3))) & 0xFF];
+          const uint32_t e = s < f.hot ? hot_rows[s * f.ncol + c] : f.trans[(size_t)s * f.ncol + c];
+          if (e == kLazyUnknownEntry) {
+            parked = true;
+            break;
+          }
+          if (e == 0) {
+            done = true;  // dead
+            break;
+          }
+          s = e & ~kLazyMatchBit;
+          if (e & kLazyMatchBit) mask |= f.now[s];
+        }
+        p += j - j0;
+        if (done && mask) atomicOr(&out[h], (unsigned long long)mask);
+      }
+      if (done || parked || phase == kLazyLongAfter) break;
+      phase = kLazyLongAtCut;
+    }
+    if (parked) {
+      const unsigned long long k = atomicAdd(npark, 1ull);
+      LazyLongPark x;
+      x.u = u;
+      x.p = p;
+      x.last = mask;
+      x.s = s;
+      x.phase = phase;
+      park[k] = x;
+      continue;
+    }
+    if (done) continue;  // (published where it finished)
+    mask |= f.eof_mask[s];  // dfa.rs:1004-1015
+    if (mask) atomicOr(&out[h], (unsigned long long)mask);
+  }
+}
+
 // find: the winner's match (find_dfa_forward, exec.rs:632-662): its end from
 // the smallest unit that matched, its start from the reverse DFA over
 // text[start..end]; an empty match at `start` starts there (exec.rs:647), a
@@ -708,6 +831,25 @@ hipError_t launch_lazy_long_finish(const BatchDev &b, const RevDfaDev &r, const 
   if (b.count == 0) return hipSuccess;
   hipLaunchKernelGGL(lazy_long_finish_kernel, dim3(grid_cap(b.count, 256, cus, 4)), dim3(256), 0, st, b, r, ures, best,
                      out);
+  return hipGetLastError();
+}
+
+hipError_t launch_lazy_set_long(const BatchDev &b, const LazyDfaDev &f, uint64_t all, uint64_t chunk,
+                                const LazyLongPark *in, uint64_t nin, LazyLongPark *park, unsigned long long *npark,
+                                uint64_t *out, hipStream_t st, int cus) {
+  if (b.offs || chunk == 0 || !f.now || !f.eof_mask || !f.reach) return hipErrorInvalidValue;
+  if (b.count == 0 || (in && nin == 0)) return hipSuccess;
+  note_fwd_path(RURE_AMD_PATH_LAZY_DFA);
+  Geo g;  // launch_set_long's
+  g.chunk = chunk;
+  g.end = ~0ull;
+  g.slots = 0;
+  const uint64_t nunits = lazy_long_units(b, chunk);
+  g.nk = nunits / b.count;
+  const uint64_t lanes = in ? nin : nunits;
+  const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>((lanes + 1023) / 1024, (uint64_t)cus * 2));
+  hipLaunchKernelGGL(lazy_set_long_kernel, dim3(grid), dim3(1024), 0, st, b, g, nunits, f, all, in, nin, park, npark,
+                     (unsigned long long *)out);
   return hipGetLastError();
 }
 

@@ -637,6 +637,9 @@ struct LazyDfaDev {
   // steps into at a unit's cut (an id without the match bit, 0 = dead,
   // 0x7FFFFFFF = not computed yet); null until a chunked call made a link
   const uint32_t *strip;
+  // per state (sets): the patterns a walk from the state can still report, or
+  // more (0 for dead); the chunked set scan leaves a unit past its cut on it
+  const uint64_t *reach;
 };
 // A lane stopped at a row not built yet: haystack, position of the byte it
 // needs, the last match end so far (~0: none; a set: the mask collected so
@@ -683,6 +686,14 @@ hipError_t launch_lazy_long(int mode, const BatchDev &b, const LazyDfaDev &f, ui
                             unsigned long long *best, hipStream_t st, int cus);
 hipError_t launch_lazy_long_finish(const BatchDev &b, const RevDfaDev &r, const uint64_t *ures,
                                    const unsigned long long *best, uint64_t *out, hipStream_t st, int cus);
+// RegexSet matches (many_matches_at) over few long fixed-stride haystacks on
+// a set's LazyDfaDev, cut into units as launch_set_long cuts them; rounds,
+// lanes and parking as launch_lazy_long (the mask a parked unit has collected
+// travels in LazyLongPark::last).  out[h], zeroed by the caller before the
+// first round, is only ever ORed into; `all` = every pattern of the set.
+hipError_t launch_lazy_set_long(const BatchDev &b, const LazyDfaDev &f, uint64_t all, uint64_t chunk,
+                                const LazyLongPark *in, uint64_t nin, LazyLongPark *park, unsigned long long *npark,
+                                uint64_t *out, hipStream_t st, int cus);
 // The units per haystack and in all for that geometry.
 inline uint64_t lazy_long_units(const BatchDev &b, uint64_t chunk) {
   const uint64_t span = b.length > b.start ? b.length - b.start : 0;

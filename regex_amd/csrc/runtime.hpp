@@ -368,7 +368,7 @@ bool lazy_device(const DevTables &tc, bool locked = false);  // locked: the call
 LazyDfa *regex_lazy(rure *re);
 DevTables *set_device(rure_set *rs, std::string *err);
 bool build_set_long(rure_set *rs);
-LazyDfa *set_lazy(rure_set *rs);
+LazyDfa *set_lazy(rure_set *rs, bool locked = false);  // locked: the caller holds rs->mu
 const SetLongDev *set_long_device(rure_set *rs, DevTables *t, std::string *err);
 uint32_t first_byte_rule(const DenseDfa &d, uint32_t ustart1, bool nonempty, uint8_t bytes[4], bool *holds);
 bool run_class(const DenseDfa &d, uint32_t ustart1, bool nonempty, uint8_t cls[256], bool ascii);
