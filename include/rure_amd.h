@@ -741,6 +741,53 @@ uint64_t rure_amd_last_set_units(uint64_t *haystacks, uint64_t *chunk);
  * search that did not take that path.  The host knows the figures: this call
  * waits for nothing. */
 uint64_t rure_amd_last_lazy_long(uint64_t *haystacks, uint64_t *chunk, uint32_t *rounds, uint32_t *fell_back);
+/* Diagnostics (host only, one value for the whole process likewise): the
+ * last find_iter (or split, replace, captures_iter) call that was cut into
+ * units on a regex's on-demand DFA: few long fixed-stride haystacks of a
+ * regex past the eager state budgets and without look-around.  units and
+ * haystacks of the batch, chunk = the unit size in bytes, rounds = the kernel
+ * rounds summed over its passes, repaired = the units iterated again from
+ * another entry than their own start, resume_passes = the extra passes the
+ * resolve step asked for, fell_back = 1 when the call gave the batch up and
+ * another engine answered.  All 0 before the first such call and after a
+ * find_iter that took another path.  Waits for nothing. */
+typedef struct rure_amd_lazy_iter_long {
+  uint64_t units, haystacks, chunk;
+  uint32_t rounds, resume_passes;
+  uint64_t repaired;
+  uint32_t fell_back, pad;
+} rure_amd_lazy_iter_long;
+void rure_amd_last_lazy_iter_long(rure_amd_lazy_iter_long *info);
+/* The resolve rule of that chunked find_iter (host only;
+ * kernels/lazy_iter_long_device.hpp, the code the device runs), over unit
+ * records the caller supplies.  An iteration state is (p, lm): the next
+ * search start and the end of the last match (~0: none); p = ~0 is the stop
+ * state.  A record: the entry state, the exit state, the matches owned, and
+ * flags (bit 0: the record exists, bit 1: its exit is clean, bits 4..: where
+ * a final record came from: 0 the speculation, 1 the fix record, 2 skipped,
+ * 3 a run the walker asked for).  haystacks * units_per records each in spec
+ * (every unit from its own start), fix (from the predecessor's exit, where
+ * that was not clean) and fin (out).  first != 0: the parallel pass fills
+ * fin, changed (a byte per unit) and zeroes walk (an entry per haystack)
+ * before the walkers run; first = 0: the walkers resume, after the caller
+ * stored the runs asked for into fin (flags: 1 | clean | 3 << 4).  Returns
+ * the number of units the walkers need run (todo, at most one per haystack,
+ * in haystack order: unit index in the batch and entry state), 0 when fin is
+ * final; RURE_AMD_ERR_ARG on a null array. */
+typedef struct rure_amd_lil_rec {
+  uint64_t entry_p, entry_lm, exit_p, exit_lm;
+  uint32_t count, flags;
+} rure_amd_lil_rec;
+typedef struct rure_amd_lil_walk {
+  uint64_t next, exit_p, exit_lm;
+  uint32_t active, clean;
+} rure_amd_lil_walk;
+typedef struct rure_amd_lil_todo {
+  uint64_t unit, p, lm;
+} rure_amd_lil_todo;
+int64_t rure_amd_lazy_iter_resolve(uint64_t haystacks, uint64_t units_per, uint64_t start, uint64_t chunk, int first,
+                                   const rure_amd_lil_rec *spec, const rure_amd_lil_rec *fix, rure_amd_lil_rec *fin,
+                                   uint8_t *changed, rure_amd_lil_walk *walk, rure_amd_lil_todo *todo);
 /* The tile kernel's skip rule (host only; kernels/tile_skip_device.hpp): a
  * regex that is, over ASCII text, one fixed sequence of m byte classes, and
  * whose packed forward DFA the host proved to leave its hot rows only at a

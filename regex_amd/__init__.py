@@ -962,6 +962,34 @@ class Regex(object):
         units = N.rure_amd_last_lazy_long(ctypes.byref(n), ctypes.byref(c), ctypes.byref(r), ctypes.byref(f))
         return int(units), int(n.value), int(c.value), int(r.value), int(f.value)
 
+    @staticmethod
+    def last_lazy_iter_long():
+        """The last find_iter (or split, replace, captures_iter) call of this
+        process that cut few long haystacks into units on the on-demand DFA,
+        as a dict: units, haystacks, chunk, rounds (summed over its passes),
+        repaired (units iterated again from another entry), resume_passes and
+        fell_back; all 0 before the first and after a find_iter that took
+        another path."""
+        info = N.LazyIterLongInfo()
+        N.rure_amd_last_lazy_iter_long(ctypes.byref(info))
+        return {k: int(getattr(info, k)) for k in ("units", "haystacks", "chunk", "rounds", "repaired",
+                                                   "resume_passes", "fell_back")}
+
+    @staticmethod
+    def lazy_iter_resolve(haystacks, units_per, start, chunk, first, spec, fix, fin, changed, walk):
+        """The resolve rule of that chunked find_iter over caller-supplied
+        unit records (rure_amd_lazy_iter_resolve: the code the device runs).
+        spec, fix, fin: ctypes arrays of _native.LilRec (haystacks * units_per
+        each), changed: a ctypes byte array of as many, walk: an array of
+        _native.LilWalk per haystack; fin, changed and walk are updated in
+        place.  Returns the units the walkers need run: [(unit, p, lm)]."""
+        todo = (N.LilTodo * max(haystacks, 1))()
+        n = N.rure_amd_lazy_iter_resolve(haystacks, units_per, start, chunk, 1 if first else 0, spec, fix, fin,
+                                         ctypes.addressof(changed), walk, todo)
+        if n < 0:
+            _check(int(n), "lazy_iter_resolve")
+        return [(int(todo[i].unit), int(todo[i].p), int(todo[i].lm)) for i in range(n)]
+
 
 def replace_all_chain(regexes, reps, haystack, length=None, capacity=None, stream=None):
     """replace_all of each regex in turn over one haystack, every step on the

@@ -253,6 +253,31 @@ rure_amd_lazy_strip_build = _sig("rure_amd_lazy_strip_build", ctypes.c_int, VP, 
 rure_amd_last_lazy_long = _sig("rure_amd_last_lazy_long", ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
                                ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32),
                                ctypes.POINTER(ctypes.c_uint32))
+class LazyIterLongInfo(ctypes.Structure):
+    _fields_ = [("units", ctypes.c_uint64), ("haystacks", ctypes.c_uint64), ("chunk", ctypes.c_uint64),
+                ("rounds", ctypes.c_uint32), ("resume_passes", ctypes.c_uint32), ("repaired", ctypes.c_uint64),
+                ("fell_back", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
+class LilRec(ctypes.Structure):
+    _fields_ = [("entry_p", ctypes.c_uint64), ("entry_lm", ctypes.c_uint64), ("exit_p", ctypes.c_uint64),
+                ("exit_lm", ctypes.c_uint64), ("count", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+class LilWalk(ctypes.Structure):
+    _fields_ = [("next", ctypes.c_uint64), ("exit_p", ctypes.c_uint64), ("exit_lm", ctypes.c_uint64),
+                ("active", ctypes.c_uint32), ("clean", ctypes.c_uint32)]
+
+
+class LilTodo(ctypes.Structure):
+    _fields_ = [("unit", ctypes.c_uint64), ("p", ctypes.c_uint64), ("lm", ctypes.c_uint64)]
+
+
+rure_amd_last_lazy_iter_long = _sig("rure_amd_last_lazy_iter_long", None, ctypes.POINTER(LazyIterLongInfo))
+rure_amd_lazy_iter_resolve = _sig("rure_amd_lazy_iter_resolve", ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64,
+                                  ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(LilRec),
+                                  ctypes.POINTER(LilRec), ctypes.POINTER(LilRec), VP, ctypes.POINTER(LilWalk),
+                                  ctypes.POINTER(LilTodo))
 rure_amd_debug_set = _sig("rure_amd_debug_set", ctypes.c_int, ctypes.c_char_p)
 rure_amd_first_byte_export = _sig("rure_amd_first_byte_export", ctypes.c_int, VP, VP)
 rure_amd_lex_export = _sig("rure_amd_lex_export", ctypes.c_int64, VP, VP, c_size, VP)

@@ -1268,6 +1268,44 @@ uint64_t rure_amd_last_set_units(uint64_t *haystacks, uint64_t *chunk) {
 uint64_t rure_amd_last_lazy_long(uint64_t *haystacks, uint64_t *chunk, uint32_t *rounds, uint32_t *fell_back) {
   return rure_amd::last_lazy_long(haystacks, chunk, rounds, fell_back);
 }
+void rure_amd_last_lazy_iter_long(rure_amd_lazy_iter_long *info) {
+  if (!info) return;
+  uint64_t v[7];
+  rure_amd::last_lazy_iter_long(v);
+  *info = rure_amd_lazy_iter_long{v[0], v[1], v[2], (uint32_t)v[3], (uint32_t)v[5], v[4], (uint32_t)v[6], 0};
+}
+
+// The records the C interface names are the kernels' own.
+static_assert(sizeof(rure_amd_lil_rec) == sizeof(rure_amd::LilRec) && offsetof(rure_amd_lil_rec, flags) == 36, "LilRec");
+static_assert(sizeof(rure_amd_lil_walk) == sizeof(rure_amd::LilWalk) && offsetof(rure_amd_lil_walk, clean) == 28,
+              "LilWalk");
+static_assert(sizeof(rure_amd_lil_todo) == sizeof(rure_amd::LilTodo), "LilTodo");
+int64_t rure_amd_lazy_iter_resolve(uint64_t haystacks, uint64_t units_per, uint64_t start, uint64_t chunk, int first,
+                                   const rure_amd_lil_rec *spec_, const rure_amd_lil_rec *fix_, rure_amd_lil_rec *fin_,
+                                   uint8_t *changed, rure_amd_lil_walk *walk_, rure_amd_lil_todo *todo_) {
+  using namespace rure_amd;
+  if (!spec_ || !fix_ || !fin_ || !changed || !walk_ || !todo_ || !units_per || !chunk) return RURE_AMD_ERR_ARG;
+  const LilRec *spec = (const LilRec *)spec_, *fix = (const LilRec *)fix_;
+  LilRec *fin = (LilRec *)fin_;
+  LilWalk *walk = (LilWalk *)walk_;
+  LilTodo *todo = (LilTodo *)todo_;
+  if (first) {
+    for (uint64_t u = 0; u < haystacks * units_per; ++u) changed[u] = lil_parallel(spec[u], fix[u], &fin[u]) ? 1 : 0;
+    memset((void *)walk, 0, haystacks * sizeof(LilWalk));
+  }
+  int64_t n = 0;
+  for (uint64_t h = 0; h < haystacks; ++h) {
+    if (walk[h].k >= units_per) continue;
+    const uint64_t u0 = h * units_per;
+    LilTodo t;
+    if (lil_walk(&walk[h], units_per, start, chunk, spec + u0, fix + u0, fin + u0, changed + u0, &t)) {
+      t.u += u0;
+      todo[n++] = t;
+    }
+  }
+  return n;
+}
+
 int rure_amd_suffix_forward(rure *re) {
   if (!re) return RURE_AMD_ERR_ARG;
   return build_iter_dfa(re) && re->suffix_fwd ? 1 : 0;

@@ -61,6 +61,22 @@ static void note_lazy_long(uint64_t units, uint64_t haystacks, uint64_t chunk, u
   memcpy(g_lazy_long, v, sizeof(v));
 }
 
+// rure_amd_last_lazy_iter_long: likewise (units, haystacks, chunk, rounds,
+// repaired units, resume passes, fell back).
+static std::mutex g_lazy_iter_long_mu;
+static uint64_t g_lazy_iter_long[7] = {0, 0, 0, 0, 0, 0, 0};
+static std::atomic<bool> g_lazy_iter_long_any{false};  // the record is not all 0
+void last_lazy_iter_long(uint64_t v[7]) {
+  std::lock_guard<std::mutex> g(g_lazy_iter_long_mu);
+  memcpy(v, g_lazy_iter_long, sizeof(g_lazy_iter_long));
+}
+static void note_lazy_iter_long(const uint64_t v[7]) {
+  if (!v[0] && !g_lazy_iter_long_any.load(std::memory_order_relaxed)) return;  // (nothing to clear)
+  std::lock_guard<std::mutex> g(g_lazy_iter_long_mu);
+  g_lazy_iter_long_any.store(v[0] != 0, std::memory_order_relaxed);
+  memcpy(g_lazy_iter_long, v, sizeof(g_lazy_iter_long));
+}
+
 // rure_amd_last_long_units: the deferred long scan's figures (haystacks,
 // chunk, units) are made on the device, so its geometry kernel writes them
 // into one pinned record of the process and each call records an event behind
@@ -315,7 +331,7 @@ static bool big_batch(const BatchDev &b, const DevTables &t) {
 }
 
 // The rounds of a batched scan on an on-demand DFA (a regex's: run_lazy,
-// run_lazy_long and run_lazy_iter; a set's: run_lazy_set and
+// run_lazy_long, run_lazy_iter and run_lazy_iter_long; a set's: run_lazy_set and
 // run_lazy_set_long): `launch` runs one round of the
 // kernel; between rounds the host builds the rows the parked lanes need (and, ahead of them,
 // more rows in discovery order) and uploads the grown table, which stays in
@@ -326,7 +342,7 @@ static bool big_batch(const BatchDev &b, const DevTables &t) {
 // *ok is then false and the caller runs the Pike VM over the whole batch
 // (the rounds' scratch is freed by then).  *rounds = the rounds launched.
 // Park is the kernel's record of a parked lane (LazyPark, LazyIterPark,
-// LazyLongPark): the rounds read its state `s` and hand the records back to
+// LazyLongPark, LazyIterLongPark): the rounds read its state `s` and hand the records back to
 // the next launch.  A chunked scan's lane may also park at its unit's cut for
 // the link of `s` (wants_link): the host makes it (LazyDfa::strip_of) and
 // builds the twin's row ahead, and the table carries the links from then on.
@@ -335,6 +351,7 @@ constexpr int kLazyRounds = 256;
 static bool wants_link(const LazyPark &) { return false; }
 static bool wants_link(const LazyIterPark &) { return false; }
 static bool wants_link(const LazyLongPark &x) { return x.phase == kLazyLongAtCut; }
+static bool wants_link(const LazyIterLongPark &x) { return x.phase == kLazyLongAtCut; }
 template <class Park, class Launch>
 static hipError_t lazy_rounds(LazyDfa &L, DevTables &t, uint64_t count, hipStream_t st, bool *ok_out, uint32_t *rounds,
                               Launch launch) {
@@ -562,6 +579,132 @@ static hipError_t run_lazy_iter(rure *re, DevTables &t, const BatchDev &b, const
   }
   *taken = true;
   return launch_iter_counts(b, off, o, st, t.cus);
+}
+
+// find_iter over few long fixed-stride haystacks of such a regex: one lane
+// per haystack (run_lazy_iter) would iterate each alone and the Pike VM gives
+// one a wave, so the iteration is cut into units as lazy_long_batch cuts the
+// search (its conditions, its chunk rule) and the units iterate on the
+// on-demand DFA (run_lazy_iter_long).  Not for a regex with look-around: a
+// unit's speculation is then not equivalent to the true iteration entering
+// earlier (iter_scan.hip's U_UNSURE and strict equivalence), and those keep
+// their path.  Knobs lazy_iter_long: 0 never, 2 at any length and count
+// (tests); lazy_chunk: the unit size in bytes.
+static bool lazy_iter_long_batch(const BatchDev &b, const DevTables &t, uint64_t *chunk) {
+  const long long mode = knob(Knob::LazyIterLong);
+  if (mode == 0 || knob(Knob::Lazy) == 0 || b.offs || b.count == 0 || !t.owner) return false;
+  if (t.has_dfa && knob(Knob::Lazy) != 1) return false;
+  if (t.owner->nt.looks_used != 0) return false;
+  const uint64_t span = b.length > b.start ? b.length - b.start : 0;
+  if (mode != 2 && (big_batch(b, t) || span < kLongSpan || b.count >= (uint64_t)t.cus * 128)) return false;
+  if (t.owner->fwd.dotstar_end == 0) return false;  // anchored at the start: no links
+  if (!lazy_device(t) || !t.owner->lazy->has_strip()) return false;
+  *chunk = unit_bytes(span, b.count, lanes_in_flight(t.cus, Knob::LongLanes), kLongFloor);
+  if (knob(Knob::LazyChunk) > 0) *chunk = std::max<uint64_t>(16, knob(Knob::LazyChunk));
+  return true;
+}
+
+// The chunked find_iter on the on-demand DFA (lazy_iter_long_device.hpp has
+// the records and the resolve rule).  Pass A: every unit iterates from
+// (c0, none).  Pass B: every unit whose predecessor left otherwise than clean
+// iterates from that exit.  Pass C: the resolve rule on the device; the units
+// its walkers still need run are iterated in one more pass each time, and the
+// walkers resume, until none is asked for.  Pass D: the unit counts scanned
+// to offsets.  Pass E: the write form over the final entries, then the
+// counts and the total.  Passes A, B and each resume pass are rounds of
+// lazy_iter_long_kernel's count form (lazy_rounds); four synchronisations
+// when no unit is asked for and every row is built.
+//
+// kLazyIterPasses: a resume pass is the walk of one unit per haystack, a lone
+// wave's work: about 4 ms by the chunked find's figures, so 64
+// of them are about what the Pike VM takes for 256 KiB, the shortest text this
+// path takes by itself.  A text that needs more (a fixed-length match repeated
+// through a long run never rejoins its speculation) is given up.
+// *taken = false where the batch is given up (a spent budget, kLazyRounds in
+// a pass, more than kLazyIterPasses resume passes, or the write form met a
+// row not built): nothing of the outputs is the answer, no scratch is held,
+// and the caller's other engines run the batch.
+constexpr uint32_t kLazyIterPasses = 64;
+static hipError_t run_lazy_iter_long(rure *re, DevTables &t, const BatchDev &b, uint64_t chunk, const IterOut &o,
+                                     hipStream_t st, bool *taken) {
+  *taken = false;
+  std::lock_guard<std::mutex> g(re->mu);
+  const uint64_t units = lazy_long_units(b, chunk);
+  const auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t sz_rec = al(units * sizeof(LilRec)), sz_changed = al(units), sz_walk = al(b.count * sizeof(LilWalk)),
+               sz_todo = al(b.count * sizeof(LilTodo)), sz_counts = al((units + 1) * 4), sz_off = al((units + 1) * 8);
+  Scratch<uint8_t> buf;
+  hipError_t e = buf.alloc(3 * sz_rec + sz_changed + sz_walk + sz_todo + sz_counts + sz_off + 256, st);
+  if (e != hipSuccess) return e;
+  uint8_t *at = buf.get();
+  const auto take = [&](size_t bytes) {
+    uint8_t *p = at;
+    at += bytes;
+    return p;
+  };
+  LilRec *spec = (LilRec *)take(sz_rec), *fix = (LilRec *)take(sz_rec), *fin = (LilRec *)take(sz_rec);
+  uint8_t *changed = take(sz_changed);
+  LilWalk *walk = (LilWalk *)take(sz_walk);
+  LilTodo *todo = (LilTodo *)take(sz_todo);
+  uint32_t *ucounts = (uint32_t *)take(sz_counts);
+  uint64_t *off = (uint64_t *)take(sz_off);
+  unsigned long long *stats = (unsigned long long *)take(64);  // units asked for, fix records
+  uint32_t *flag = (uint32_t *)take(64);
+  if ((e = hipMemsetAsync(stats, 0, 128, st)) != hipSuccess) return e;
+  uint64_t rec[7] = {units, b.count, chunk, 0, 0, 0, 0};
+  LazyDfaDev table{};  // the last round's: every row and link the batch reads is in it
+  bool ok = true;
+  const auto pass = [&](int from, const LilRec *ent, uint64_t ntodo, LilRec *out) {
+    uint32_t rounds = 0;
+    const hipError_t pe = lazy_rounds<LazyIterLongPark>(
+        *re->lazy, t, from == kLilList ? ntodo : units, st, &ok, &rounds,
+        [&](const LazyDfaDev &f, const LazyIterLongPark *in, uint64_t nin, LazyIterLongPark *po,
+            unsigned long long *cnt) {
+          table = f;
+          return launch_lazy_iter_long_count(b, f, t.lr, chunk, from, ent, todo, ntodo, in, nin, po, cnt, out, stats,
+                                             st, t.cus);
+        });
+    rec[3] += rounds;
+    return pe;
+  };
+  const auto give_up = [&]() {
+    rec[6] = 1;
+    note_lazy_iter_long(rec);
+    return hipSuccess;
+  };
+  if ((e = pass(kLilFresh, nullptr, 0, spec)) != hipSuccess) return e;
+  if (!ok) return give_up();
+  if ((e = pass(kLilAfter, spec, 0, fix)) != hipSuccess) return e;
+  if (!ok) return give_up();
+  unsigned long long host[2] = {0, 0};
+  for (bool first = true;; first = false) {
+    if ((e = launch_lazy_iter_long_resolve(b, chunk, first, spec, fix, fin, changed, walk, todo, stats, st, t.cus)) !=
+            hipSuccess ||
+        (e = hipMemcpyAsync(host, stats, 16, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+        (e = hipStreamSynchronize(st)) != hipSuccess)
+      return e;
+    if (first) rec[4] = host[1];
+    const uint64_t ntodo = host[0];
+    if (ntodo == 0) break;
+    if (ntodo > b.count) return hipErrorUnknown;  // (a walker asks for one unit at a time)
+    if (++rec[5] > kLazyIterPasses) return give_up();
+    rec[4] += ntodo;
+    if ((e = pass(kLilList, nullptr, ntodo, fin)) != hipSuccess) return e;
+    if (!ok) return give_up();
+    if ((e = hipMemsetAsync(stats, 0, 8, st)) != hipSuccess) return e;
+  }
+  uint32_t unknown = 0;
+  if ((e = launch_lazy_iter_long_counts(b, chunk, fin, ucounts, st, t.cus)) != hipSuccess) return e;
+  if ((e = scan_counts(ucounts, off, units, st)) != hipSuccess) return e;
+  if ((e = launch_lazy_iter_long_write(b, table, t.lr, chunk, fin, off, o.matches, o.cap, flag, st, t.cus)) !=
+      hipSuccess)
+    return e;
+  if ((e = hipMemcpyAsync(&unknown, flag, 4, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+  if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
+  if (unknown) return give_up();
+  *taken = true;
+  note_lazy_iter_long(rec);
+  return launch_iter_counts(b, off, o, st, t.cus, units / b.count);
 }
 
 // Offset batches (documents of their own lengths) of find / is_match /
@@ -1191,6 +1334,8 @@ static hipError_t find_iter_full(const IterCall &c, const FwdDfaDev &fi, const I
 // The batched find_iter (re_trait.rs:197-221) on one stream.
 hipError_t run_find_iter(rure *re, DevTables *t, const BatchDev &b, const IterOut &o, hipStream_t st,
                          std::string *err, const IterSpan *sp) {
+  const uint64_t none[7] = {0, 0, 0, 0, 0, 0, 0};
+  note_lazy_iter_long(none);  // (run_lazy_iter_long records its call)
   if (!sp && t->anchored_rev && b.start > 0 && b.count) return find_iter_anchored_rev(*t, b, o, st);
   if (lane_search_ok(*t) && !sp) {
     const hipError_t e = find_iter_suffix(*t, b, o, st);
@@ -1212,8 +1357,15 @@ hipError_t run_find_iter(rure *re, DevTables *t, const BatchDev &b, const IterOu
   // device (lazy_batch; knob lazy=1: any regex that can have it, ahead of the
   // chunked engines): every search of the iteration on the on-demand DFA, as
   // the reference's lazy DFA serves them whatever the state count.  Whole
-  // haystacks only.  Where it gives the batch up, the engines below answer.
-  if (!sp && b.count && !lane_search_ok(*t) && lazy_batch(b, *t)) {
+  // haystacks only.  Few long fixed-stride haystacks of such a regex
+  // (lazy_iter_long_batch) are cut into units that iterate on it.  Where
+  // either gives the batch up, the engines below answer.
+  uint64_t lchunk = 0;
+  if (!sp && b.count && !lane_search_ok(*t) && lazy_iter_long_batch(b, *t, &lchunk)) {
+    bool taken = false;
+    const hipError_t e = run_lazy_iter_long(re, *t, b, lchunk, o, st, &taken);
+    if (e != hipSuccess || taken) return e;
+  } else if (!sp && b.count && !lane_search_ok(*t) && lazy_batch(b, *t)) {
     bool taken = false;
     const hipError_t e = run_lazy_iter(re, *t, b, o, st, &taken);
     if (e != hipSuccess || taken) return e;

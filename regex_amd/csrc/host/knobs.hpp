@@ -54,6 +54,7 @@ enum class Knob : int {
   LazyLong,        // 0: few long haystacks of a regex past the eager budgets keep the Pike VM; 2: chunked on the on-demand DFA at any length and count
   LazyChunk,       // the unit size in bytes of that chunked scan (floor 16, no odd-lines rounding)
   TileSkip,        // 0: the tile kernel never skips a tile's walk (tile_skip_device.hpp)
+  LazyIterLong,    // 0: find_iter over few long haystacks of such a regex keeps its path; 2: chunked on the on-demand DFA at any length and count (unit size: lazy_chunk)
   kCount
 };
 

@@ -10,7 +10,8 @@
 // eagerly (dfa_build.cpp, column form) so a lane only reads tables.  Past
 // that budget too, rows are built on demand between rounds of
 // lazy_dfa_kernel (a regex), lazy_long_kernel (its few long haystacks, cut
-// into units), lazy_iter_kernel (its find_iter), lazy_set_kernel (a
+// into units), lazy_iter_kernel (its find_iter; lazy_iter_long_kernel over
+// few long haystacks), lazy_set_kernel (a
 // RegexSet's matches) or lazy_set_long_kernel (its few long haystacks).
 //
 // Execution: one lane per haystack (lazy_long_kernel: per unit).  A 16-byte chunk's columns come from the
@@ -793,6 +794,267 @@ __global__ __launch_bounds__(256) void lazy_long_finish_kernel(BatchDev bt, RevD
   }
 }
 
+// find_iter over few long fixed-stride haystacks on the on-demand DFA: the
+// iteration of lazy_iter_kernel, one lane per unit of lazy_long_kernel's
+// geometry.  A unit's iteration runs from an entry state (ip, lm) while ip is
+// before its cut c1 and owns the matches that start before c1: each search is
+// lazy_long_kernel's bounded one from ip (through c1 - 1, into strip[s] there,
+// on until the automaton dies or the text ends, then the EOF step; the unit
+// that owns the end has no cut), then lazy_iter_kernel's delayed match flag,
+// rev_scan for the start and iter_next's step rule.  The unit ends when ip
+// reaches c1 (exit (ip, lm), clean when ip == c1 and no match ended there),
+// when a search finds nothing (exit: the state that search began in, clean:
+// no match starts between there and c1, so the next unit's iteration is a
+// fresh one) or on a reverse NoMatch (the stop exit: the haystack's iteration
+// is over).  Which entries a round's fresh lanes take: kLilFresh .. kLilFinal
+// (dfa_scan.hpp); how the records are combined: lazy_iter_long_device.hpp.
+//
+// One loop as lazy_iter_kernel (a 16-byte block, the step into the link, or
+// the end of a search and the begin of the next per pass), staging and the
+// next block's load in flight as lazy_long_kernel.  A lane parks on a row not
+// built, or at the cut on a link not computed, with the iteration's state and
+// the search's, and the next round resumes it inside that search.  WRITE as
+// lazy_iter_kernel's: it runs once over the final entries, stops after the
+// matches the count form found, and sets *flag where it would have parked.
+template <bool WRITE>
+__global__ __launch_bounds__(1024) void lazy_iter_long_kernel(
+    BatchDev bt, Geo g, uint64_t nunits, LazyDfaDev f, RevDfaDev r, uint32_t from, const LilRec *ent,
+    const LilTodo *todo, uint64_t ntodo, const LazyIterLongPark *in, uint64_t nin, LazyIterLongPark *park,
+    unsigned long long *npark, LilRec *out, unsigned long long *stats, const uint64_t *off, uint64_t *matches,
+    uint64_t cap, uint32_t *flag) {
+  __shared__ __attribute__((aligned(16))) uint32_t hot_rows[kBigLdsBytes / 4];
+  __shared__ uint8_t colmap[256];
+  const uint32_t nhot = f.hot * f.ncol;
+  for (uint32_t i = threadIdx.x; i < nhot; i += blockDim.x) hot_rows[i] = f.trans[i];
+  for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x) colmap[i] = f.colmap[i];
+  __syncthreads();
+  const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
+  const uint64_t nl = in ? nin : from == kLilList ? ntodo : nunits;
+  for (uint64_t l = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; l < nl; l += nthreads) {
+    const uint64_t u = in ? in[l].u : from == kLilList ? todo[l].u : l;
+    if (u >= nunits) continue;
+    uint64_t h, len, c0, c1;  // c1 == NONE: the unit that owns the end
+    const uint8_t *base;
+    unit_bounds<false>(bt, g, u, &h, &base, &len, &c0, &c1);
+    uint64_t ip = c0, lm = NONE, cnt = 0, want = NONE;  // the iteration
+    uint64_t p = 0, last = NONE;                        // the search
+    uint32_t s = 0, phase = kLazyLongAfter;
+    bool searching = false, parked = false;
+    if (in) {
+      ip = in[l].ip;
+      lm = in[l].lm;
+      cnt = in[l].count;
+      p = in[l].p;
+      last = in[l].last;
+      s = in[l].s;
+      phase = in[l].phase;
+      searching = true;
+    } else {
+      if (from == kLilAfter) {
+        if (u % g.nk == 0) {
+          out[u].flags = 0;
+          continue;
+        }
+        const LilRec pr = ent[u - 1];
+        if (pr.flags & kLilClean) {
+          out[u].flags = 0;
+          continue;
+        }
+        atomicAdd(&stats[1], 1ull);
+        if (lil_steps_over(pr.xp, c1)) {
+          out[u] = lil_skip(pr.xp, pr.xlm, c1);
+          continue;
+        }
+        ip = pr.xp;
+        lm = pr.xlm;
+      } else if (from == kLilList) {
+        ip = todo[l].p;
+        lm = todo[l].lm;
+      } else if (from == kLilFinal) {
+        const LilRec fr = ent[u];
+        if (fr.count == 0) continue;
+        ip = fr.ep;
+        lm = fr.elm;
+        want = fr.count;
+      }
+      if (!WRITE) {
+        out[u].ep = ip;
+        out[u].elm = lm;
+      }
+    }
+    uint64_t xp = ip, xlm = lm;  // the exit, as long as the search under way finds nothing
+    bool xclean = true;
+    uintptr_t nblk = 0;  // the block `nxt` holds (0: none)
+    uint4 nxt = make_uint4(0, 0, 0, 0);
+    while (true) {
+      if (!searching) {
+        if (WRITE && cnt >= want) break;
+        xp = ip;
+        xlm = lm;
+        if (ip >= c1) {
+          xclean = ip == c1 && lm != c1;
+          break;
+        }
+        xclean = true;
+        if (ip > len) break;
+        s = f.start[fwd_flag_index(base, len, ip)] & ~kLazyMatchBit;
+        if (s == 0) break;  // dead start state (dfa.rs:484)
+        p = ip;
+        last = NONE;
+        phase = c1 == NONE ? kLazyLongAfter : kLazyLongBefore;
+        searching = true;
+      }
+      bool done = false;
+      if (phase == kLazyLongAtCut) {
+        const uint32_t e = f.strip ? f.strip[s] : kLazyUnknownEntry;
+        if (e == kLazyUnknownEntry) {
+          parked = true;
+          break;
+        }
+        if (e == 0) {
+          done = true;  // no thread started before the cut is alive
+        } else {
+          s = e;
+          phase = kLazyLongAfter;
+        }
+      }
+      if (!done) {
+        const uint64_t lim = phase == kLazyLongBefore ? c1 - 1 : len;
+        if (p < lim) {
+          const uintptr_t a = (uintptr_t)(base + p), blk = a & ~(uintptr_t)15;
+          const uint4 v = blk == nblk ? nxt : *(const uint4 *)blk;
+          if (blk + 16 < (uintptr_t)(base + len)) {
+            nblk = blk + 16;
+            nxt = *(const uint4 *)nblk;
+          }
+          const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+          const uint32_t j0 = (uint32_t)(a & 15);
+          const uint32_t n = (uint32_t)min<uint64_t>(16 - j0, lim - p);
+          uint32_t j = j0;
+          for (; j < j0 + n; ++j) {
+            const uint32_t c = colmap[(w[j >> 2] >> (8 * (j & 3))) & 0xFF];
+            const uint32_t e = s < f.hot ? hot_rows[s * f.ncol + c] : f.trans[(size_t)s * f.ncol + c];
+            if (e == kLazyUnknownEntry) {
+              parked = true;
+              break;
+            }
+            if (e == 0) {
+              done = true;  // dead
+              break;
+            }
+            s = e & ~kLazyMatchBit;
+            if (e & kLazyMatchBit) last = p + (j - j0);  // dfa.rs:658-668: Match(at - 1)
+          }
+          p += j - j0;
+          if (parked) break;
+          if (!done && p < lim) continue;  // the next block
+        }
+        if (!done && phase == kLazyLongBefore) {
+          phase = kLazyLongAtCut;
+          continue;
+        }
+      }
+      // the search is over: the automaton died, or the text ended
+      searching = false;
+      if (!done && f.eof[s]) last = len;  // dfa.rs:748-763
+      if (last == NONE) break;
+      uint64_t ms = ip;  // exec.rs:647
+      if (last != ip) {
+        ms = rev_scan(r, nullptr, base, len, ip, last);
+        if (ms == NONE || ms == QUITMARK) {  // exec.rs:656-660 (no quit state here): the stop exit
+          xp = xlm = NONE;
+          xclean = false;
+          break;
+        }
+      }
+      if (ms == last) {
+        ip = last + 1;
+        if (lm == last) continue;
+      } else {
+        ip = last;
+      }
+      lm = last;
+      if (WRITE) {
+        const uint64_t k = off[u] + cnt;
+        if (k < cap) {
+          matches[2 * k] = ms;
+          matches[2 * k + 1] = last;
+        }
+      }
+      ++cnt;
+    }
+    if (parked) {
+      if (WRITE) {
+        *flag = 1;
+        continue;
+      }
+      const unsigned long long k = atomicAdd(npark, 1ull);
+      LazyIterLongPark x;
+      x.u = u;
+      x.ip = ip;
+      x.lm = lm;
+      x.count = cnt;
+      x.p = p;
+      x.last = last;
+      x.s = s;
+      x.phase = phase;
+      park[k] = x;
+      continue;
+    }
+    if (!WRITE) {
+      out[u].xp = xp;
+      out[u].xlm = xlm;
+      out[u].count = (uint32_t)cnt;
+      out[u].flags = kLilHas | (xclean ? kLilClean : 0) | (from == kLilList ? (uint32_t)kLilRun << kLilSrcShift : 0);
+    }
+  }
+}
+
+// Pass C (lazy_iter_long_device.hpp): the parallel pass, one lane per unit ...
+__global__ __launch_bounds__(256) void lazy_iter_long_parallel_kernel(uint64_t nunits, uint64_t nh, const LilRec *spec,
+                                                                      const LilRec *fix, LilRec *fin,
+                                                                      uint8_t *changed, LilWalk *walk) {
+  const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x, t0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (uint64_t u = t0; u < nunits; u += nthreads) {
+    LilRec f;
+    changed[u] = lil_parallel(spec[u], fix[u], &f) ? 1 : 0;
+    fin[u] = f;
+  }
+  for (uint64_t h = t0; h < nh; h += nthreads) {
+    LilWalk w;
+    w.k = w.xp = w.xlm = 0;
+    w.active = w.xclean = 0;
+    walk[h] = w;
+  }
+}
+
+// ... and the walkers, one lane per haystack: a haystack has few changed
+// units (a match that crosses a cut and leaves the next unit otherwise than
+// its own speculation did), and a walk between them is a chain of record
+// loads, no DFA.
+__global__ __launch_bounds__(64) void lazy_iter_long_walk_kernel(uint64_t nh, uint64_t nk, uint64_t start,
+                                                                 uint64_t chunk, const LilRec *spec, const LilRec *fix,
+                                                                 LilRec *fin, const uint8_t *changed, LilWalk *walk,
+                                                                 LilTodo *todo, unsigned long long *stats) {
+  for (uint64_t h = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; h < nh; h += (uint64_t)gridDim.x * blockDim.x) {
+    LilWalk w = walk[h];
+    if (w.k >= nk) continue;
+    const uint64_t u0 = h * nk;
+    LilTodo t;
+    if (lil_walk(&w, nk, start, chunk, spec + u0, fix + u0, fin + u0, changed + u0, &t)) {
+      t.u += u0;
+      todo[atomicAdd(&stats[0], 1ull)] = t;
+    }
+    walk[h] = w;
+  }
+}
+
+__global__ __launch_bounds__(256) void lazy_iter_long_counts_kernel(uint64_t nunits, const LilRec *fin,
+                                                                    uint32_t *ucounts) {
+  for (uint64_t u = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; u <= nunits; u += (uint64_t)gridDim.x * blockDim.x)
+    ucounts[u] = u < nunits ? fin[u].count : 0;
+}
+
 template <int MODE>
 hipError_t launch_lazy_long_m(const BatchDev &b, const Geo &g, uint64_t nunits, const LazyDfaDev &f,
                               const LazyLongPark *in, uint64_t nin, LazyLongPark *park, unsigned long long *npark,
@@ -824,6 +1086,77 @@ hipError_t launch_lazy_long(int mode, const BatchDev &b, const LazyDfaDev &f, ui
       return launch_lazy_long_m<MODE_ISMATCH>(b, g, nunits, f, in, nin, park, npark, ures, best, st, cus);
     default: return launch_lazy_long_m<MODE_SHORTEST>(b, g, nunits, f, in, nin, park, npark, ures, best, st, cus);
   }
+}
+
+static Geo lazy_long_geo(const BatchDev &b, uint64_t chunk, uint64_t *nunits) {
+  Geo g;  // long_scan_m's
+  g.chunk = chunk;
+  g.end = ~0ull;
+  g.slots = 0;
+  *nunits = lazy_long_units(b, chunk);
+  g.nk = *nunits / b.count;
+  return g;
+}
+
+hipError_t launch_lazy_iter_long_count(const BatchDev &b, const LazyDfaDev &f, const RevDfaDev &r, uint64_t chunk,
+                                       int from, const LilRec *ent, const LilTodo *todo, uint64_t ntodo,
+                                       const LazyIterLongPark *in, uint64_t nin, LazyIterLongPark *park,
+                                       unsigned long long *npark, LilRec *out, unsigned long long *stats,
+                                       hipStream_t st, int cus) {
+  if (b.offs || chunk == 0 || from < kLilFresh || from > kLilList) return hipErrorInvalidValue;
+  if (b.count == 0 || (in && nin == 0) || (!in && from == kLilList && ntodo == 0)) return hipSuccess;
+  note_fwd_path(RURE_AMD_PATH_LAZY_DFA);
+  uint64_t nunits;
+  const Geo g = lazy_long_geo(b, chunk, &nunits);
+  const uint64_t lanes = in ? nin : from == kLilList ? ntodo : nunits;
+  const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>((lanes + 1023) / 1024, (uint64_t)cus * 2));
+  hipLaunchKernelGGL((lazy_iter_long_kernel<false>), dim3(grid), dim3(1024), 0, st, b, g, nunits, f, r, (uint32_t)from,
+                     ent, todo, ntodo, in, nin, park, npark, out, stats, (const uint64_t *)nullptr,
+                     (uint64_t *)nullptr, (uint64_t)0, (uint32_t *)nullptr);
+  return hipGetLastError();
+}
+
+hipError_t launch_lazy_iter_long_write(const BatchDev &b, const LazyDfaDev &f, const RevDfaDev &r, uint64_t chunk,
+                                       const LilRec *fin, const uint64_t *off, uint64_t *matches, uint64_t cap,
+                                       uint32_t *flag, hipStream_t st, int cus) {
+  if (b.offs || chunk == 0) return hipErrorInvalidValue;
+  if (b.count == 0) return hipSuccess;
+  uint64_t nunits;
+  const Geo g = lazy_long_geo(b, chunk, &nunits);
+  const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>((nunits + 1023) / 1024, (uint64_t)cus * 2));
+  hipLaunchKernelGGL((lazy_iter_long_kernel<true>), dim3(grid), dim3(1024), 0, st, b, g, nunits, f, r,
+                     (uint32_t)kLilFinal, fin, (const LilTodo *)nullptr, (uint64_t)0,
+                     (const LazyIterLongPark *)nullptr, (uint64_t)0, (LazyIterLongPark *)nullptr,
+                     (unsigned long long *)nullptr, (LilRec *)nullptr, (unsigned long long *)nullptr, off, matches, cap,
+                     flag);
+  return hipGetLastError();
+}
+
+hipError_t launch_lazy_iter_long_resolve(const BatchDev &b, uint64_t chunk, bool first, const LilRec *spec,
+                                         const LilRec *fix, LilRec *fin, uint8_t *changed, LilWalk *walk,
+                                         LilTodo *todo, unsigned long long *stats, hipStream_t st, int cus) {
+  if (b.offs || chunk == 0) return hipErrorInvalidValue;
+  if (b.count == 0) return hipSuccess;
+  uint64_t nunits;
+  const Geo g = lazy_long_geo(b, chunk, &nunits);
+  if (first) {
+    hipLaunchKernelGGL(lazy_iter_long_parallel_kernel, dim3(grid_cap(nunits, 256, cus, 8)), dim3(256), 0, st, nunits,
+                       b.count, spec, fix, fin, changed, walk);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(lazy_iter_long_walk_kernel, dim3(grid_cap(b.count, 64, cus, 128)), dim3(64), 0, st, b.count,
+                     g.nk, b.start, chunk, spec, fix, fin, (const uint8_t *)changed, walk, todo, stats);
+  return hipGetLastError();
+}
+
+hipError_t launch_lazy_iter_long_counts(const BatchDev &b, uint64_t chunk, const LilRec *fin, uint32_t *ucounts,
+                                        hipStream_t st, int cus) {
+  if (b.offs || chunk == 0) return hipErrorInvalidValue;
+  const uint64_t nunits = lazy_long_units(b, chunk);
+  hipLaunchKernelGGL(lazy_iter_long_counts_kernel, dim3(grid_cap(nunits + 1, 256, cus, 8)), dim3(256), 0, st, nunits,
+                     fin, ucounts);
+  return hipGetLastError();
 }
 
 hipError_t launch_lazy_long_finish(const BatchDev &b, const RevDfaDev &r, const uint64_t *ures,

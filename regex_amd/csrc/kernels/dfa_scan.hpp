@@ -6,6 +6,7 @@
 #include "../../../include/rure_amd.h"
 #include "../host/chunk_plan.hpp"
 #include "../host/knobs.hpp"
+#include "lazy_iter_long_device.hpp"
 #include "tile_skip_device.hpp"
 
 namespace rure_amd {
@@ -572,6 +573,10 @@ void note_set_units(uint64_t units, uint64_t haystacks, uint64_t chunk);
 // instead, of the last chunked on-demand DFA call (rure_amd_last_lazy_long;
 // all 0 after a regex search that did not take that path).
 uint64_t last_lazy_long(uint64_t *haystacks, uint64_t *chunk, uint32_t *rounds, uint32_t *fell_back);
+// The last chunked find_iter on the on-demand DFA (rure_amd_last_lazy_iter_long;
+// all 0 after a find_iter that took another path): v = units, haystacks, unit
+// size, rounds summed over the passes, repaired units, resume passes, fell back.
+void last_lazy_iter_long(uint64_t v[7]);
 // Kernel timer (rure_amd_kernel_timer): HIP event pairs around bracketed launches.
 void ktimer_begin(hipStream_t st);
 void ktimer_end(hipStream_t st);
@@ -724,7 +729,58 @@ hipError_t launch_lazy_iter_write(const BatchDev &b, const LazyDfaDev &f, const 
 // off[0..n] = the exclusive sums of counts[0..n) (u32; off[n] = their
 // total), and from them o.counts per haystack and o.total.
 hipError_t scan_counts(const uint32_t *counts, uint64_t *off, uint64_t n, hipStream_t st);
-hipError_t launch_iter_counts(const BatchDev &b, const uint64_t *off, const IterOut &o, hipStream_t st, int cus);
+// (nk: off holds nk entries per haystack, the units of a chunked engine)
+hipError_t launch_iter_counts(const BatchDev &b, const uint64_t *off, const IterOut &o, hipStream_t st, int cus,
+                              uint64_t nk = 1);
+
+// find_iter over few long fixed-stride haystacks on a regex's LazyDfaDev, cut
+// into units as launch_lazy_long cuts them (lazy_iter_long_kernel; the records
+// and the resolve rule: lazy_iter_long_device.hpp).  A unit's iteration runs
+// from an entry state and owns the matches that start before its cut: every
+// search is bounded by the cut as lazy_long_kernel bounds it.  A lane stopped
+// at a row not built yet, or at the cut on a link not computed (phase
+// kLazyLongAtCut): the unit, the iteration's state (ip: the start of the
+// search under way, lm: the end of the last match or ~0, count: the matches
+// so far) and that search's (p: the position of the byte it needs, last: its
+// last match end so far or ~0, s: the state, phase: where in the bounded
+// search it stood).
+struct LazyIterLongPark {
+  uint64_t u, ip, lm, count, p, last;
+  uint32_t s, phase;
+};
+// Where a round's fresh lanes take their entries from, and what they are:
+enum {
+  kLilFresh = 0,  // every unit, from (c0, none)
+  kLilAfter = 1,  // every unit but a haystack's first whose predecessor's record in `ent` has no clean
+                  // exit, from that exit; a unit that exit steps over gets its record without a walk,
+                  // every other unit none (flags 0).  stats[1] += the records made.
+  kLilList = 2,   // the units of `todo` (ntodo of them), from the states listed; their records are
+                  // marked kLilRun
+  kLilFinal = 3,  // (write form) every unit whose record in `ent` has matches, from that record's entry
+};
+// One round of the count form: lanes are the fresh ones `from` names (in =
+// nullptr) or the lanes parked by the previous round; a finished lane writes
+// the unit's record (entry, matches owned, exit, clean) into out[u].
+hipError_t launch_lazy_iter_long_count(const BatchDev &b, const LazyDfaDev &f, const RevDfaDev &r, uint64_t chunk,
+                                       int from, const LilRec *ent, const LilTodo *todo, uint64_t ntodo,
+                                       const LazyIterLongPark *in, uint64_t nin, LazyIterLongPark *park,
+                                       unsigned long long *npark, LilRec *out, unsigned long long *stats,
+                                       hipStream_t st, int cus);
+// The write form, once: match k of unit u goes to record off[u] + k when that
+// is below cap.  *flag (device, zeroed) is set should it meet a row or link
+// not built.
+hipError_t launch_lazy_iter_long_write(const BatchDev &b, const LazyDfaDev &f, const RevDfaDev &r, uint64_t chunk,
+                                       const LilRec *fin, const uint64_t *off, uint64_t *matches, uint64_t cap,
+                                       uint32_t *flag, hipStream_t st, int cus);
+// Pass C on the device.  first: the parallel pass (fin, changed[u], walk
+// zeroed) before the walkers; else the walkers resume.  A walker that needs a
+// unit run appends it to todo (stats[0] = their number, zeroed by the
+// caller).  ucounts[u] = fin[u].count for every unit, ucounts[nunits] = 0.
+hipError_t launch_lazy_iter_long_resolve(const BatchDev &b, uint64_t chunk, bool first, const LilRec *spec,
+                                         const LilRec *fix, LilRec *fin, uint8_t *changed, LilWalk *walk,
+                                         LilTodo *todo, unsigned long long *stats, hipStream_t st, int cus);
+hipError_t launch_lazy_iter_long_counts(const BatchDev &b, uint64_t chunk, const LilRec *fin, uint32_t *ucounts,
+                                        hipStream_t st, int cus);
 
 // Scratch device memory for the scans, cached by the library (scratch.cpp):
 // a freed block is kept with an event recorded on the freeing stream and

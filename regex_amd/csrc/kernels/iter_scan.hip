@@ -2622,9 +2622,10 @@ hipError_t scan_counts(const uint32_t *counts, uint64_t *off, uint64_t n, hipStr
   return e != hipSuccess ? e : e2;
 }
 
-hipError_t launch_iter_counts(const BatchDev &b, const uint64_t *off, const IterOut &o, hipStream_t st, int cus) {
+hipError_t launch_iter_counts(const BatchDev &b, const uint64_t *off, const IterOut &o, hipStream_t st, int cus,
+                              uint64_t nk) {
   hipLaunchKernelGGL(iter_counts_kernel, dim3(grid_cap(b.count, 256, cus, 4)), dim3(256), 0, st, b.count,
-                     (uint64_t)1, (const uint64_t *)nullptr, off, o.counts, o.total, b);
+                     nk, (const uint64_t *)nullptr, off, o.counts, o.total, b);
   return hipGetLastError();
 }
 
