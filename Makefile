@@ -13,7 +13,8 @@ KERNEL_SRC = regex_amd/csrc/kernels/dfa_scan.hip regex_amd/csrc/kernels/nfa_scan
              regex_amd/csrc/kernels/replace_scan.hip regex_amd/csrc/kernels/gather_scan.hip \
              regex_amd/csrc/kernels/match_types.hip regex_amd/csrc/kernels/big_dfa.hip \
              regex_amd/csrc/kernels/run_iter.hip regex_amd/csrc/kernels/long_scan.hip \
-             regex_amd/csrc/kernels/expand_scan.hip regex_amd/csrc/kernels/set_long.hip
+             regex_amd/csrc/kernels/expand_scan.hip regex_amd/csrc/kernels/set_long.hip \
+             regex_amd/csrc/kernels/records.hip
 KERNEL_OBJ = $(patsubst regex_amd/csrc/kernels/%.hip,$(OBJDIR)/%.o,$(KERNEL_SRC))
 HDRS = $(wildcard regex_amd/csrc/host/*.hpp regex_amd/csrc/host/*.h regex_amd/csrc/kernels/*.hpp include/*.h)
 OBJDIR = regex_amd/build

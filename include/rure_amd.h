@@ -230,6 +230,37 @@ int rure_amd_set_matches_batch_words(rure_set *re, const rure_amd_batch *batch, 
 int rure_amd_find_iter_batch(rure *re, const rure_amd_batch *batch, uint64_t *counts, rure_match *matches,
                              size_t capacity, uint64_t *total, void *stream);
 
+/* Device grep: the matching records (lines) of one raw text buffer.  `text`
+ * (device; alignment and readability as rure_amd_batch.haystack) holds
+ * `length` bytes with the byte `delim` between records: a record starts at
+ * offset 0 and after every `delim`, provided that start is < length, and ends
+ * before the next `delim` or at `length` ("a\nb" and "a\nb\n" hold 2 records,
+ * "\n" one empty record, an empty text none).  The delimiter is never part of
+ * a record and the bytes around a record never influence its answer: record r
+ * is selected iff rure_is_match(re, its bytes, its length, 0) is true (false
+ * with RURE_AMD_RECORDS_INVERT), for every regex, with `^`, `$` and `\b`
+ * evaluated at the record's edges.
+ * Outputs (device; the record-output rules above): *nrecords = the records of
+ * the text, *total = the selected ones (exact whatever `capacity` is),
+ * records[j] = (start, end) in text offsets of the j-th selected record in
+ * text order, numbers[j] (may be NULL) = its 0-based record index,
+ * *pike_served (may be NULL) = the records the Pike VM answered (where the
+ * DFA quit on a Unicode word boundary next to a non-ASCII byte; every record
+ * of a regex without an eager DFA).  At most `capacity` entries of records
+ * and numbers are written.
+ * The text is cut into units of the long scan's size, and a unit's lane
+ * answers the records that start in it (kernels/records_device.hpp;
+ * rure_amd_last_records tells): a search never crosses a delimiter, so the
+ * units need no repair.  The call only enqueues work on `stream`: it never
+ * waits and reads nothing back (the first call of a regex on a device uploads
+ * its tables, as for every batched call).  Bad arguments (a NULL regex, text
+ * with a length, nrecords or total, records with a capacity; an unknown flag):
+ * RURE_AMD_ERR_ARG, nothing launched.  rure_amd_last_fwd_path is left alone. */
+#define RURE_AMD_RECORDS_INVERT (1u << 0)   /* select the records that do NOT match (grep -v) */
+int rure_amd_match_records(rure *re, const uint8_t *text, size_t length, uint8_t delim, uint32_t flags,
+                           uint64_t *nrecords, uint64_t *total, rure_match *records, uint64_t *numbers,
+                           size_t capacity, uint64_t *pike_served, void *stream);
+
 /* find_iter over one span [lo, hi) of a long haystack (sharded or streamed
  * iteration): the iteration of re_trait.rs:197-221 restricted to
  * the matches that START in [lo, hi) (a match may end past hi; the haystack
@@ -732,6 +763,20 @@ uint64_t rure_amd_last_long_units(uint64_t *haystacks, uint64_t *chunk);
  * 64-pattern group's, for larger sets) that did not chunk.  The host knows
  * the geometry: this call waits for nothing. */
 uint64_t rure_amd_last_set_units(uint64_t *haystacks, uint64_t *chunk);
+/* Diagnostics (host only, one value for the whole process likewise): the
+ * units the last rure_amd_match_records call cut its text into; *chunk (may
+ * be NULL) = the unit size in bytes.  0, 0 before the first such call and
+ * after one over an empty text.  The host knows both: this call waits for
+ * nothing. */
+uint64_t rure_amd_last_records(uint64_t *chunk);
+/* The ownership rule of that call (host only; kernels/records_device.hpp, the
+ * code the device runs) over a host text: for each unit u of `chunk` bytes
+ * (>= 1), first[u] = the first record start it owns (SIZE_MAX: none) and
+ * count[u] = how many records it owns, for the units below `cap` (first and
+ * count may be NULL).  Returns the number of units, ceil(length / chunk);
+ * RURE_AMD_ERR_ARG for a NULL text with a length or a chunk of 0. */
+int64_t rure_amd_records_units(const uint8_t *text, size_t length, uint8_t delim, size_t chunk,
+                               uint64_t *first, uint64_t *count, size_t cap);
 /* Diagnostics (host only, one value for the whole process likewise): the
  * units the last chunked find / is_match / shortest_match (or captures
  * bounds) call on a regex's on-demand DFA cut its batch into; *haystacks =

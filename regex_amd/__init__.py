@@ -699,6 +699,65 @@ class Regex(object):
                 return counts, out[: min(t, cap)]
             cap = t
 
+    def match_records(self, buf, delim=b"\n", invert=False, length=None, capacity=None, numbers=True, stream=None,
+                      info=None):
+        """Device grep (rure_amd_match_records): the records of one raw text
+        buffer (a torch CUDA uint8 tensor; `delim`, one byte, between records)
+        that match, or with invert=True those that do not.  The delimiter is
+        never part of a record, and `^`, `$` and `\\b` see the record's edges.
+        Returns (records, numbers, nrecords): records = (k, 2) int64 (start,
+        end) text offsets of the selected records in text order, numbers =
+        (k,) int64 their 0-based record indices (None with numbers=False),
+        nrecords = the records of the text.  With capacity=None the buffers
+        are sized from a first call with capacity 0; else at most `capacity`
+        records come back.  The C call never waits; this wrapper synchronises
+        the stream to read the totals.  info (a dict, optional) receives
+        "total" (the selected records, whatever the capacity) and
+        "pike_served" (the records the Pike VM answered)."""
+        import torch
+        if not isinstance(buf, torch.Tensor) or not buf.is_cuda or buf.dtype != torch.uint8 or not buf.is_contiguous():
+            raise TypeError("buf must be a contiguous torch CUDA (HIP) uint8 tensor")
+        if not isinstance(delim, (bytes, bytearray)) or len(delim) != 1:
+            raise TypeError("delim must be one byte")
+        n = buf.numel() if length is None else length
+        if n > buf.numel():
+            raise ValueError("length exceeds the buffer")
+        dev = buf.device
+        head = torch.zeros((3,), dtype=torch.int64, device=dev)  # nrecords, total, pike_served
+        flags = N.RECORDS_INVERT if invert else 0
+        s = stream or torch.cuda.current_stream()
+
+        def call(cap, rec, num):
+            _check(N.rure_amd_match_records(self._re, ctypes.c_void_p(buf.data_ptr()), n, delim[0], flags,
+                                            ctypes.c_void_p(head.data_ptr()), ctypes.c_void_p(head.data_ptr() + 8),
+                                            ctypes.c_void_p(rec.data_ptr()) if rec is not None else None,
+                                            ctypes.c_void_p(num.data_ptr()) if num is not None else None, cap,
+                                            ctypes.c_void_p(head.data_ptr() + 16), _stream_ptr(stream)),
+                   "match_records")
+            s.synchronize()
+            return [int(x) for x in head.cpu().tolist()]
+
+        cap = capacity
+        if cap is None:
+            cap = call(0, None, None)[1]
+        rec = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=dev)
+        num = torch.empty((max(cap, 1),), dtype=torch.int64, device=dev) if numbers else None
+        nrecords, total, served = call(cap, rec, num)
+        if info is not None:
+            info["total"] = total
+            info["pike_served"] = served
+        k = min(total, cap)
+        return rec[:k], (num[:k] if numbers else None), nrecords
+
+    @staticmethod
+    def last_records():
+        """(units, chunk) of the last match_records call of this process: the
+        units its text was cut into and their size in bytes; (0, 0) before
+        the first and after one over an empty text.  Waits for nothing."""
+        c = ctypes.c_uint64(0)
+        units = N.rure_amd_last_records(ctypes.byref(c))
+        return int(units), int(c.value)
+
     def find_iter_span(self, haystack, lo, hi, length=None, entry=None, capacity=None, stream=None):
         """find_iter restricted to the matches starting in [lo, hi) of one long
         haystack (rure_amd_find_iter_span; sharded / streamed iteration).

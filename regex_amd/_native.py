@@ -235,6 +235,12 @@ rure_amd_tile_skip_info = _sig("rure_amd_tile_skip_info", ctypes.c_int, VP, ctyp
 rure_amd_tile_skip_simulate = _sig("rure_amd_tile_skip_simulate", ctypes.c_int64, VP, VP, c_size, VP, VP, VP)
 rure_amd_last_set_units = _sig("rure_amd_last_set_units", ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
                                ctypes.POINTER(ctypes.c_uint64))
+RECORDS_INVERT = 1 << 0
+rure_amd_match_records = _sig("rure_amd_match_records", ctypes.c_int, VP, VP, c_size, ctypes.c_uint8, ctypes.c_uint32,
+                              VP, VP, VP, VP, c_size, VP, VP)
+rure_amd_last_records = _sig("rure_amd_last_records", ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64))
+rure_amd_records_units = _sig("rure_amd_records_units", ctypes.c_int64, VP, c_size, ctypes.c_uint8, c_size, VP, VP,
+                              c_size)
 rure_amd_set_long_dfa_export = _sig("rure_amd_set_long_dfa_export", ctypes.c_int, VP, ctypes.POINTER(DfaInfo), VP, VP,
                                     VP, VP, VP, VP)
 class LazyInfo(ctypes.Structure):

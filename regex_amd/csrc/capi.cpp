@@ -500,6 +500,13 @@ int rure_amd_find_iter_batch(rure *re, const rure_amd_batch *batch, uint64_t *co
   return run_find_iter(re, t, b, o, (hipStream_t)stream, &err) == hipSuccess ? RURE_AMD_OK : RURE_AMD_ERR_HIP;
 }
 
+int rure_amd_match_records(rure *re, const uint8_t *text, size_t length, uint8_t delim, uint32_t flags,
+                           uint64_t *nrecords, uint64_t *total, rure_match *records, uint64_t *numbers,
+                           size_t capacity, uint64_t *pike_served, void *stream) {
+  return run_match_records(re, text, length, delim, flags, nrecords, total, (uint64_t *)records, numbers, capacity,
+                           pike_served, (hipStream_t)stream);
+}
+
 int64_t rure_amd_literals_export(rure *re, uint32_t *lens, uint8_t *bytes, size_t cap) {
   if (!re) return RURE_AMD_ERR_ARG;
   build_iter_dfa(re);
@@ -1264,6 +1271,28 @@ uint64_t rure_amd_last_long_units(uint64_t *haystacks, uint64_t *chunk) {
 }
 uint64_t rure_amd_last_set_units(uint64_t *haystacks, uint64_t *chunk) {
   return rure_amd::last_set_units(haystacks, chunk);
+}
+uint64_t rure_amd_last_records(uint64_t *chunk) { return rure_amd::last_records(chunk); }
+// The device's walk (RecWalk) over a copy of the text placed as the caller's
+// is within its 16-byte block, the blocks' other bytes holding delimiters:
+// the search loads whole blocks, and what lies around the text must not count.
+int64_t rure_amd_records_units(const uint8_t *text, size_t length, uint8_t delim, size_t chunk, uint64_t *first,
+                               uint64_t *count, size_t cap) {
+  using namespace rure_amd;
+  if ((!text && length) || !chunk) return RURE_AMD_ERR_ARG;
+  std::vector<uint8_t> buf(length + 48, delim);
+  uint8_t *base = buf.data() + ((16 - ((uintptr_t)buf.data() & 15)) & 15) + ((uintptr_t)text & 15);
+  if (length) memcpy(base, text, length);
+  const uint64_t units = rec_units(length, chunk);
+  const uint32_t rep = delim * 0x01010101u;
+  for (uint64_t u = 0; u < units && u < cap; ++u) {
+    RecWalk w(base, length, chunk, u, rep);
+    if (first) first[u] = w.more() ? w.s : ~0ull;
+    uint64_t n = 0;
+    for (; w.more(); w.next()) ++n;
+    if (count) count[u] = n;
+  }
+  return (int64_t)units;
 }
 uint64_t rure_amd_last_lazy_long(uint64_t *haystacks, uint64_t *chunk, uint32_t *rounds, uint32_t *fell_back) {
   return rure_amd::last_lazy_long(haystacks, chunk, rounds, fell_back);

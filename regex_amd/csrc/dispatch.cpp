@@ -41,6 +41,20 @@ void note_set_units(uint64_t units, uint64_t haystacks, uint64_t chunk) {
   g_set_units[2] = chunk;
 }
 
+// rure_amd_last_records: likewise (units, chunk).
+static std::mutex g_records_mu;
+static uint64_t g_records[2] = {0, 0};
+uint64_t last_records(uint64_t *chunk) {
+  std::lock_guard<std::mutex> g(g_records_mu);
+  if (chunk) *chunk = g_records[1];
+  return g_records[0];
+}
+void note_records(uint64_t units, uint64_t chunk) {
+  std::lock_guard<std::mutex> g(g_records_mu);
+  g_records[0] = units;
+  g_records[1] = chunk;
+}
+
 // rure_amd_last_lazy_long: likewise (units, haystacks, chunk, rounds, fell back).
 static std::mutex g_lazy_long_mu;
 static uint64_t g_lazy_long[5] = {0, 0, 0, 0, 0};
@@ -1111,6 +1125,61 @@ int search_batch(int mode, rure *re, const rure_amd_batch *batch, void *out, hip
   const FwdDfaDev *iter = long_batch(mode, b, *t, &chunk) ? iter_device(re, *t, &err) : ragged_long_iter(re, b, *t);
   if (b.offs && !iter) note_long_none();
   return run_regex(mode, b, *t, out, st, grid, iter) == hipSuccess ? RURE_AMD_OK : RURE_AMD_ERR_HIP;
+}
+
+
+// rure_amd_match_records: the records of one delimited text that match
+// (kernels/records.hip).  The unit size is the long scan's (long_batch's rule
+// over the whole text; knob records_chunk overrides it), the forward DFA
+// answers each record from its start, and the Pike VM, gated on the device,
+// the records it quit on -- or all of them for a regex without an eager DFA
+// (the on-demand DFA does not run records).  Everything is enqueued on grids
+// fixed by the length: nothing is read back.  rure_amd_last_fwd_path is not
+// touched: the call is its own path.
+int run_match_records(rure *re, const uint8_t *text, size_t length, uint8_t delim, uint32_t flags, uint64_t *nrecords,
+                      uint64_t *total, uint64_t *records, uint64_t *numbers, size_t capacity, uint64_t *pike_served,
+                      hipStream_t st) {
+  if (!re || (!text && length) || !nrecords || !total || (!records && capacity) ||
+      (flags & ~(uint32_t)RURE_AMD_RECORDS_INVERT))
+    return RURE_AMD_ERR_ARG;
+  std::string err;
+  DevTables *t = regex_device(re, &err);
+  if (!t) return err.rfind("HIP", 0) == 0 ? RURE_AMD_ERR_HIP : RURE_AMD_ERR_DFA;
+  if (!t->has_dfa && !re->nfa_ok) return RURE_AMD_ERR_DFA;
+  const auto rc = [](hipError_t e) { return e == hipSuccess ? RURE_AMD_OK : RURE_AMD_ERR_HIP; };
+  hipError_t e = pike_served ? hipMemsetAsync(pike_served, 0, 8, st) : hipSuccess;
+  if (length == 0) {  // no record
+    note_records(0, 0);
+    if (e == hipSuccess) e = hipMemsetAsync(nrecords, 0, 8, st);
+    if (e == hipSuccess) e = hipMemsetAsync(total, 0, 8, st);
+    return rc(e);
+  }
+  uint64_t chunk = unit_bytes(length, 1, lanes_in_flight(t->cus, Knob::LongLanes), kLongFloor);
+  if (knob(Knob::RecordsChunk) > 0) chunk = std::max<uint64_t>(16, knob(Knob::RecordsChunk));
+  const uint64_t units = rec_units(length, chunk);
+  note_records(units, chunk);
+  size_t zeroed = 0;
+  Scratch<> block;
+  if (e == hipSuccess) e = block.alloc(records_scratch_bytes(length, units, &zeroed), st);
+  if (e != hipSuccess) return rc(e);
+  const RecordsScratch s = records_scratch_at(block.get(), length, units);
+  e = hipMemsetAsync(block.get(), 0, zeroed, st);
+  if (e == hipSuccess) e = launch_records_scan(text, length, delim, chunk, t->has_dfa ? &t->f : nullptr, s, st, t->cus);
+  Scratch<> lists;  // the Pike VM's waves, where their lists do not fit the LDS
+  if (e == hipSuccess && (!t->has_dfa || t->quit_possible)) {
+    const int grid = records_pike_grid(length, t->n, t->cus);
+    const size_t wb = nfa_wave_bytes(t->n.nleaves);
+    if (wb > kNfaLdsMax) e = lists.alloc(wb * (size_t)grid, st);
+    if (e == hipSuccess)
+      e = launch_records_pike(text, length, delim, chunk, t->n, s, (unsigned long long *)pike_served, lists.get(), st,
+                              grid);
+  }
+  if (e == hipSuccess) e = scan_counts(s.owned, s.owned_off, units, st);
+  if (e == hipSuccess) e = scan_counts(s.selected, s.selected_off, units, st);
+  if (e == hipSuccess)
+    e = launch_records_write(text, length, delim, chunk, (flags & RURE_AMD_RECORDS_INVERT) != 0, s, nrecords, total,
+                             records, numbers, capacity, st, t->cus);
+  return rc(e);
 }
 
 

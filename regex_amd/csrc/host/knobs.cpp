@@ -22,7 +22,7 @@ const char *const kNames[kN] = {
     "iter_ragged", "iter_bs",    "long_lanes",  "core_bs",    "core_lds",   "core_prof",  "scratch_cap", "timing",
     "replace_generic", "chain_seq", "shadow_sync", "iter_wave", "wave_cu", "wave_split", "wave_tables", "wave_lds",
     "long_ragged", "long_chunk", "long_list", "set_long", "set_chunk", "lazy_long", "lazy_chunk",
-    "tileskip",   "lazy_iter_long",
+    "tileskip",   "lazy_iter_long", "records_chunk",
 };
 
 std::atomic<long long> g_val[kN];

@@ -55,6 +55,7 @@ enum class Knob : int {
   LazyChunk,       // the unit size in bytes of that chunked scan (floor 16, no odd-lines rounding)
   TileSkip,        // 0: the tile kernel never skips a tile's walk (tile_skip_device.hpp)
   LazyIterLong,    // 0: find_iter over few long haystacks of such a regex keeps its path; 2: chunked on the on-demand DFA at any length and count (unit size: lazy_chunk)
+  RecordsChunk,    // the unit size in bytes of the record scan (floor 16)
   kCount
 };
 

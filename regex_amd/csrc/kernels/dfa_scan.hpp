@@ -7,6 +7,7 @@
 #include "../host/chunk_plan.hpp"
 #include "../host/knobs.hpp"
 #include "lazy_iter_long_device.hpp"
+#include "records_device.hpp"
 #include "tile_skip_device.hpp"
 
 namespace rure_amd {
@@ -604,6 +605,44 @@ hipError_t launch_dfa_set(const BatchDev &b, const SetDfaDev &f, uint64_t *out, 
 // *units = the units the batch was cut into.
 hipError_t launch_set_long(const BatchDev &b, const SetLongDev &f, uint64_t chunk, uint64_t *out, hipStream_t st,
                            int cus, uint64_t *units);
+
+// The matching records of one delimited text (records.hip; the ownership rule:
+// records_device.hpp).  The text is cut into units of `chunk` bytes; every
+// launch runs on a grid fixed by `length`, nothing is read back.
+struct RecordsScratch {
+  uint32_t *sel_bits;    // bit p: the record starting at p is selected (before INVERT); (length + 31) / 32 words
+  uint32_t *quit_bits;   // bit p: the DFA quit on the record starting at p (left to the Pike VM)
+  uint32_t *quit_word;   // raised when any record quit
+  uint32_t *owned;       // per unit (+ 1 entry): the records it owns
+  uint32_t *selected;    // per unit (+ 1 entry): those with their bit in sel_bits
+  uint64_t *owned_off;   // their exclusive sums (units + 1 entries)
+  uint64_t *selected_off;
+};
+// The layout of one scratch block holding it all: its size, and the bytes
+// from its start that must be zero before the scan (the bitmaps and the word).
+size_t records_scratch_bytes(uint64_t length, uint64_t units, size_t *zeroed);
+RecordsScratch records_scratch_at(void *block, uint64_t length, uint64_t units);
+// The scan: one lane per unit walks its records through f (is_match from each
+// record's start; f null: no eager DFA, every record is marked as quit).
+hipError_t launch_records_scan(const uint8_t *text, uint64_t length, uint8_t delim, uint64_t chunk,
+                               const FwdDfaDev *f, const RecordsScratch &s, hipStream_t st, int cus);
+// The Pike VM over the records whose bit is in quit_bits (returns at once
+// while quit_word is 0): sets sel_bits, adds to `selected` and to *served
+// (may be null).  scratch: the waves' lists when they do not fit the LDS
+// (grid * nfa_wave_bytes), else null.
+int records_pike_grid(uint64_t length, const NfaDev &n, int cus);
+hipError_t launch_records_pike(const uint8_t *text, uint64_t length, uint8_t delim, uint64_t chunk, const NfaDev &n,
+                               const RecordsScratch &s, unsigned long long *served, void *scratch, hipStream_t st,
+                               int grid);
+// After scan_counts over owned and selected: *nrecords, *total, and the
+// selected (invert: the others) records' (start, end) and numbers (may be
+// null) below cap, in text order.
+hipError_t launch_records_write(const uint8_t *text, uint64_t length, uint8_t delim, uint64_t chunk, bool invert,
+                                const RecordsScratch &s, uint64_t *nrecords, uint64_t *total, uint64_t *records,
+                                uint64_t *numbers, uint64_t cap, hipStream_t st, int cus);
+// The units and unit size of the last record scan (rure_amd_last_records).
+uint64_t last_records(uint64_t *chunk);
+void note_records(uint64_t units, uint64_t chunk);
 
 // An automaton past the u16 tables (more than 65535 states, host
 // kBigDfaRawStates budget): u32 next states in column form, trans[s * ncol +

@@ -395,6 +395,9 @@ bool to_batch(const rure_amd_batch *b, BatchDev *o);
 bool single_call(rure *re, int mode, const uint8_t *hay, size_t len, size_t start, uint64_t *r0, uint64_t *r1);
 uint64_t set_single_call(rure_set *rs, const uint8_t *hay, size_t len, size_t start);
 int search_batch(int mode, rure *re, const rure_amd_batch *batch, void *out, hipStream_t st);
+int run_match_records(rure *re, const uint8_t *text, size_t length, uint8_t delim, uint32_t flags, uint64_t *nrecords,
+                      uint64_t *total, uint64_t *records, uint64_t *numbers, size_t capacity, uint64_t *pike_served,
+                      hipStream_t st);
 int set_batch_word(rure_set *rs, const BatchDev &b, uint64_t *mask, hipStream_t stream);
 int set_batch_group(rure_set *g, const rure_amd_batch *batch, const BatchDev &b, uint64_t *mask, size_t words,
                     size_t w, hipStream_t st);
